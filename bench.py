@@ -11,8 +11,14 @@ n = 13 193 787 549 keys x 13 bytes (171.5 GB), exact index, hash.checksum.bits=4
 m = n/1500+1 = 8 795 859 buckets.  It fits one MI355X, so N=1 runs the whole
 set; with --gpus N the same key set is sharded N ways (strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n KEYS] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-keys KEYS] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds every other figure after the timed steps (the single-pass A/B,
+the full-build and end-to-end legs, the E4 leg at N > 1, the CPU baselines;
+--no-cpu / --no-full-build / --e4-devices 0 drop legs of it).  --dump-outputs
+DIR writes what the last timed step returned, for comparing two builds.
 """
 from __future__ import annotations
 
@@ -49,6 +55,34 @@ def _oracle():
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle as O
     return O
+
+
+DUMP_TOTAL_BYTES = 64 << 20   # --dump-outputs never writes more than this in all
+DUMP_FULL_BYTES = 40 << 20    # an output up to this size is written whole
+DUMP_SAMPLE_ELEMS = 1 << 20   # a larger one: this many elements at fixed positions
+DUMP_SEED = 0x62736462
+
+
+def dump_outputs(d: str, outputs: dict):
+    """--dump-outputs: the tensors the last timed step returned, as d/<name>.npy.
+    `outputs` maps a name to (tensor, numpy dtype); the dtype holds the values
+    exactly (bucket counts < 2^24 in float32, edge offsets < 2^53 in float64).
+    An output too large to be written whole is sampled at DUMP_SAMPLE_ELEMS
+    positions drawn once from DUMP_SEED (sorted, the last element always among
+    them), so the positions depend on the output's length alone."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_TOTAL_BYTES
+    for name, (t, dtype) in outputs.items():
+        if t.numel() * np.dtype(dtype).itemsize > min(DUMP_FULL_BYTES, left):
+            rng = np.random.default_rng(DUMP_SEED)
+            pos = np.sort(rng.choice(t.numel() - 1, DUMP_SAMPLE_ELEMS - 1, replace=False))
+            pos = np.append(pos, t.numel() - 1)
+            t = t[torch.from_numpy(pos).to(t.device)]
+        a = t.cpu().numpy().astype(dtype)
+        left -= a.nbytes
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline(m: int, target_s: float, threads: int):
@@ -509,10 +543,15 @@ def main():
     ap.add_argument("--num-keys", dest="n", type=int, default=README_N, help="total keys (all ranks)")
     ap.add_argument("--mode", type=int, default=0, help="0 auto/partitioned, 2 direct atomics")
     ap.add_argument("--chunk", type=int, default=0, help="keys per partitioned chunk (0 = default)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (bucket counts, edge offsets) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other figure: single-pass A/B, full-build and "
+                         "end-to-end legs, the E4 leg over the ranks, CPU baselines")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use")
-    ap.add_argument("--no-full-build", action="store_true", help="skip the full-build figures")
+    ap.add_argument("--no-full-build", action="store_true", help="--full: skip the full-build figures")
     ap.add_argument("--e4-devices", type=int, default=1,
                     help="GPUs of the one-process E4 full-build figure (0 = skip it); never more than asked")
     ap.add_argument("--e4-keys", type=int, default=0,
@@ -523,6 +562,10 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend (nccl = RCCL over xGMI; gloo only to rehearse N ranks on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run is the headline alone: every other leg belongs to --full
+        args.no_cpu = args.no_full_build = True
 
     import torch
     import torch.distributed as dist
@@ -656,6 +699,10 @@ def main():
     total = int(E[-1].item())
     ok = total == n
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"counts": (counts, "float32"), "edge_offsets": (E, "float64")})
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
     if rank == 0:
         value = n * args.steps / dt
         p1_avg_s = p1_ms / 1e3 / max(p1_launches, 1)
@@ -743,6 +790,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": dt * 1e3 / args.steps,
             "higher_is_better": True,
             "scaling": "strong",
