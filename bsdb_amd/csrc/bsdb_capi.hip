@@ -516,7 +516,7 @@ using D13Kernel = void (*)(P1Args, uint64_t);
 // k_pass1_vare (BSDB_D13_VARIANT 1, 4: its profiling variants).  13-byte keys (BSDB_D13_VARIANT): 0 k_pass1_d13e
 // (production), 1 its hash-and-bins-only profile (results invalid), 2 the
 // round-1 sort kernel k_pass1_d13, 4 k_pass1_d13e with phase stamps over
-// counts[] (results invalid).
+// counts[] (results invalid), 13 k_pass1_d13e with a buffer cursor atomic.
 struct D13Sel {
     D13Kernel k;
     int nt;             // workgroup size
@@ -554,6 +554,8 @@ D13Sel d13_select(const bsdb_ctx *c, bool var = false, uint32_t key_len = 13, bo
         case 1: return {k_pass1_d13e<1>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
         case 4: return {k_pass1_d13e<4>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
         case 12: return {k_pass1_d13e<12>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
+        case 13:  // (results valid) the cursor atomic as a range-checked buffer atomic
+            return {seed0 ? k_pass1_d13e<13, true> : k_pass1_d13e<13>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
         case 2:
             if (c->d13_threads == 256) return {k_pass1_d13<256>, 256, 256 * P1_KEYS_PER_THREAD, 512, false, 0};
             return {k_pass1_d13<512>, 512, 512 * P1_KEYS_PER_THREAD, 1024, false, 0};

@@ -599,6 +599,9 @@ constexpr uint16_t ID_PAD = 0xFFFF;                       // not a local id (ids
 // 12 = everything but the hash: the same loads, bins, cursor atomics and
 // write-out with a 2-instruction stand-in bucket (uniform over [0, m) for
 // random key bytes) -- what pass 1's memory traffic alone costs.
+// 13 (results valid) = the cursor atomic as a range-checked buffer atomic:
+// the lanes without a partition send nothing to memory (0.15 ms of pass 1 at
+// C4, inside the run-to-run spread: not the default).
 // L: the key length, 13 or an aligned 8 / 12 / 16 (the same design; the
 // 16-byte window of a key then starts at the key itself).
 template <int VARIANT, bool SEED0 = false, int L = 13>
@@ -625,6 +628,14 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     const uint32_t PPW = (P + NW - 1) / NW;
     const bool owner = (uint32_t)l < PPW && (uint32_t)w * PPW + l < P;
     const uint32_t my_p = owner ? (uint32_t)w * PPW + l : P;  // P = none
+    // VARIANT 13: the cursor words of the ncopy region copies, and nothing
+    // else, behind a buffer descriptor; a lane without a partition passes an
+    // offset past them, so the range check drops its atomic (the words there
+    // are the tail kernel's cursors and the scratch: adding 0 to them would
+    // be harmless too)
+    constexpr bool BUF_ATOMIC = VARIANT == 13;
+    const uint32_t cur_bytes = a.ncopy * P * 4u;
+    const auto cur_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.cursor, 0, (int)cur_bytes, 0x00020000);
 
     u32x4a S[4][D13_Q];
     // Key kt of a tile starts at byte L * kt of it; tile, quarter and key
@@ -632,6 +643,11 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     // lane's 4-byte-aligned window offset and its byte shift are the same
     // for every key it loads: the address is a uniform base (scalar
     // arithmetic) + one 32-bit lane offset, no per-key VALU.
+    // (Wave w's slot s covers bytes [L*NT*s + 64*L*w, +64*L + 3] of the tile:
+    // at L = 13 that is 6.5 lines, so a wave shares lines with its
+    // neighbours.  The wave-contiguous mapping -- wave w takes bytes
+    // [L*NT*w, L*NT*(w+1)), a quarter's four loads 26 whole lines -- costs no
+    // instruction and was measured at no gain)
     const uint32_t lane_off = ((uint32_t)tid * L) & ~3u;
     const uint32_t sh = (((uint32_t)tid * L) & 3u) * 8u;  // (0 for L = 8, 12, 16)
     static_assert((NT * L) % 4 == 0 && ((uint64_t)TILE * L) % 4 == 0, "window alignment per lane");
@@ -715,8 +731,17 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         // the remainder to the bin's start, for the tile after next (after
         // this wave's chunk reads in program order; that tile hashes after
         // the coming barrier)
-        if (my_p < P && c8_prev)
-            for (uint32_t e = 0; e < rm_prev; ++e) bins[prev][my_p * CAPB + e] = bins[prev][my_p * CAPB + c8_prev + e];
+        // One aligned 16-byte move (c8_prev and CAPB are multiples of 8 ids;
+        // rm_prev > 0 means c8_prev + 8 <= CAPB, so the read stays in the
+        // bin).  Slots rm_prev..7 receive stale ids: the re-armed counter
+        // ranks the tile after next on top of rm_prev, and no slot at or past
+        // a bin's count is ever read.  (An id-by-id loop, up to 7 dependent
+        // LDS round trips per wave right before the barrier, cost 0.4 ms of
+        // pass 1 at C4.)
+        if (my_p < P && c8_prev && rm_prev) {
+            uint16_t *const b0 = &bins[prev][my_p * CAPB];
+            *reinterpret_cast<uint4 *>(b0) = *reinterpret_cast<const uint4 *>(b0 + c8_prev);
+        }
     };
 
 #pragma unroll
@@ -769,7 +794,10 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         // write-out's wait for it then covers nothing younger).  Lanes of one
         // instruction must not share a word: same-word lanes are serialised
         // at the memory side (measured 6x slower).
-        if (VARIANT != 1)
+        if constexpr (BUF_ATOMIC)
+            b_prev = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(
+                (int)c8_prev, cur_rsrc, my_p < P ? (copy * P + my_p) * 4u : cur_bytes + 4u * l, 0, 0);
+        else if (VARIANT != 1)
             b_prev = atomicAdd(my_p < P ? a.cursor + copy * P + my_p : a.scratch + P1_SCRATCH_WG + blockIdx.x * 1024 + tid,
                                c8_prev);
         copy_prev = copy;

@@ -1,0 +1,48 @@
+"""Verdicts of the pass-1 request A/B (profiles/pass1_requests/).
+
+Reads DIR/<name>.jsonl (bench.py result lines of alternated runs, one file
+per library: parent, req_a, req_b, req_c, all) and prints, per library, the
+median / min / max of ms_per_step and of pass 1's kernel time, and whether
+its median gain over the parent exceeds the parent's own max - min spread
+(the bar a change has to clear to stay in the default kernel).
+usage: python tools/pass1_requests_verdict.py DIR [OUT_JSON]"""
+import json
+import os
+import statistics
+import sys
+
+
+def column(path, get):
+    return [get(json.loads(line)) for line in open(path) if line.strip()]
+
+
+def main():
+    d = sys.argv[1]
+    fields = {"ms_per_step": lambda r: r["ms_per_step"], "pass1_ms": lambda r: r["kernel_ms_per_step"]["pass1"]}
+    out = {}
+    for name in ("parent", "req_a", "req_b", "req_c", "all"):
+        path = os.path.join(d, name + ".jsonl")
+        if not os.path.exists(path):
+            continue
+        out[name] = {}
+        for f, get in fields.items():
+            v = column(path, get)
+            out[name][f] = {"runs": v, "median": statistics.median(v), "min": min(v), "max": max(v)}
+    for name, o in out.items():
+        for f in fields:
+            p = out["parent"][f]
+            spread = p["max"] - p["min"]
+            gain = p["median"] - o[f]["median"]
+            o[f]["gain_vs_parent_median"] = gain
+            o[f]["parent_spread"] = spread
+            o[f]["clears_spread"] = name != "parent" and gain > spread
+    for name, o in out.items():
+        print(name, " ".join(f"{f}: median {o[f]['median']:.3f} [{o[f]['min']:.3f}, {o[f]['max']:.3f}] "
+                             f"gain {o[f]['gain_vs_parent_median']:+.3f} (spread {o[f]['parent_spread']:.3f}) "
+                             f"{'CLEARS' if o[f]['clears_spread'] else '-'}" for f in fields))
+    if len(sys.argv) > 2:
+        json.dump(out, open(sys.argv[2], "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
