@@ -57,8 +57,7 @@ struct bsdb_ctx {
     int hist_mode = 0;
     int frontend = 0;  // 13-byte keys: 0 auto (pipelined), 1 LDS-staged, 2 direct per-tile
     int num_cus = 256;
-    int d13_variant = 0;  // profiling only (BSDB_D13_VARIANT): results are NOT valid when != 0
-    int d13_threads = 512;  // workgroup size of the pipelined 13-byte kernel (BSDB_D13_THREADS=256|512)
+    int d13_variant = 0;  // 13-byte keys' pass-1 kernel (BSDB_D13_VARIANT, see pass1_select): the same results under each
     int d13_copies = 8;     // region copies of the binned 13-byte kernel (BSDB_D13_COPIES=8|16|32)
     uint64_t chunk_keys = 0;
     int fused = -1;  // 13-byte keys, single-pass kernel: -1 = what mode 0 picks (BSDB_FUSED), 0 off, 1 on
@@ -512,68 +511,70 @@ uint64_t round64(double x) { return ((uint64_t)x + 63) & ~63ULL; }
 
 using D13Kernel = void (*)(P1Args, uint64_t);
 
-// The persistent pass-1 kernel a context runs.  Variable-length keys:
-// k_pass1_vare (BSDB_D13_VARIANT 1, 4: its profiling variants).  13-byte keys (BSDB_D13_VARIANT): 0 k_pass1_d13e
-// (production), 1 its hash-and-bins-only profile (results invalid), 2 the
-// round-1 sort kernel k_pass1_d13, 4 k_pass1_d13e with phase stamps over
-// counts[] (results invalid), 13 k_pass1_d13e with a buffer cursor atomic.
-struct D13Sel {
-    D13Kernel k;
-    int nt;             // workgroup size
-    uint64_t tile;      // keys per tile
-    uint32_t maxp;      // partitions (bins) supported
-    bool binned;        // runs padded to 8 ids, region copies = d13_copies
-    uint32_t bin_ids;   // binned: ids per LDS bin buffer
+// The persistent pass-1 kernel of a key set and its bin layout, or none: the
+// one-tile-per-workgroup kernels of launch_pass1.
+struct Pass1Sel {
+    D13Kernel k;         // nullptr: none
+    int nt;              // workgroup size
+    uint64_t tile;       // keys per tile
+    bool binned;         // runs padded to 8 ids, region copies = d13_copies
+    bool windowed;       // fixed-length keys read as 16-byte windows (k_pass1_d13e, k_pass1_d13), not k_pass1_vare
+    uint32_t bin_shift;  // region bins: bucket >> bin_shift
+    uint32_t nparts;
+    uint32_t capb;       // binned: ids per LDS bin
 };
-// Fixed key lengths the windowed kernel k_pass1_d13e serves (a key's 16-byte
-// window from its aligned start); BSDB_NO_FIXED_WINDOW=1 sends 8/12/16 to the
-// var-len kernel instead (A/B switch for measurements).
-bool windowed_len(uint32_t key_len) {
-    return key_len == 13 || ((key_len == 8 || key_len == 12 || key_len == 16) && !getenv("BSDB_NO_FIXED_WINDOW"));
-}
-
-D13Sel d13_select(const bsdb_ctx *c, bool var = false, uint32_t key_len = 13, bool seed0 = false) {
-    if (!var && key_len != 13 && windowed_len(key_len)) {
-        D13Kernel k = key_len == 8    ? (seed0 ? k_pass1_d13e<0, true, 8> : k_pass1_d13e<0, false, 8>)
-                      : key_len == 12 ? (seed0 ? k_pass1_d13e<0, true, 12> : k_pass1_d13e<0, false, 12>)
-                                      : (seed0 ? k_pass1_d13e<0, true, 16> : k_pass1_d13e<0, false, 16>);
-        return {k, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-    }
-    if (!var && key_len != 13)  // every other fixed length: the var-len kernel on k * L offsets
-        return {seed0 ? k_pass1_vare<0, true, true> : k_pass1_vare<0, true>, VARE_NT, VARE_TILE, VARE_MAXP, true,
-                VARE_BIN_IDS};
-    if (var) {
-        D13Kernel k = seed0 ? k_pass1_vare<0, false, true> : k_pass1_vare<0, false>;
-        if (c->d13_variant == 1) k = k_pass1_vare<1, false>;
-        if (c->d13_variant == 4) k = k_pass1_vare<4, false>;
-        if (c->d13_variant == 5) k = k_pass1_vare<5, false>;
-        if (c->d13_variant == 6) k = k_pass1_vare<6, false>;
-        return {k, VARE_NT, VARE_TILE, VARE_MAXP, true, VARE_BIN_IDS};
-    }
-    switch (c->d13_variant) {
-        case 1: return {k_pass1_d13e<1>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-        case 4: return {k_pass1_d13e<4>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-        case 12: return {k_pass1_d13e<12>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-        case 13:  // (results valid) the cursor atomic as a range-checked buffer atomic
-            return {seed0 ? k_pass1_d13e<13, true> : k_pass1_d13e<13>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-        case 2:
-            if (c->d13_threads == 256) return {k_pass1_d13<256>, 256, 256 * P1_KEYS_PER_THREAD, 512, false, 0};
-            return {k_pass1_d13<512>, 512, 512 * P1_KEYS_PER_THREAD, 1024, false, 0};
-        default:
-            return {seed0 ? k_pass1_d13e<0, true> : k_pass1_d13e<0>, D13E_NT, D13E_TILE, D13E_MAXP, true, D13E_BIN_IDS};
-    }
-}
 
 // Bins of a binned kernel: the smallest bin_shift with ceil(m >> shift) <=
-// sel.maxp, so a tile fills each LDS bin to tile/P on average while a bin
-// holds bin_ids/P >= 2.25x that (>= 8 sigma).
-bool binned_layout(const D13Sel &sel, uint64_t m, uint32_t &shift, uint32_t &nbins, uint32_t &capb) {
-    shift = 0;
-    while (shift <= (uint32_t)PART_SHIFT && ((m + (1ULL << shift) - 1) >> shift) > (uint64_t)sel.maxp) ++shift;
+// maxp, so a tile fills each LDS bin to tile/P on average while a bin holds
+// bin_ids/P >= 2.25x that (>= 8 sigma).
+bool binned_layout(Pass1Sel &sel, uint32_t maxp, uint32_t bin_ids, uint64_t m) {
+    uint32_t shift = 0;
+    while (shift <= (uint32_t)PART_SHIFT && ((m + (1ULL << shift) - 1) >> shift) > (uint64_t)maxp) ++shift;
     if (shift > (uint32_t)PART_SHIFT) return false;
-    nbins = (uint32_t)((m + (1ULL << shift) - 1) >> shift);
-    capb = std::min<uint32_t>((sel.bin_ids / nbins) & ~7u, (uint32_t)sel.tile + 8);
+    sel.bin_shift = shift;
+    sel.nparts = (uint32_t)((m + (1ULL << shift) - 1) >> shift);
+    sel.capb = std::min<uint32_t>((bin_ids / sel.nparts) & ~7u, (uint32_t)sel.tile + 8);
     return true;
+}
+
+// The one place that chooses pass 1's kernel (two-pass path, m buckets):
+//  * 13-byte keys: k_pass1_d13e (BSDB_D13_VARIANT=13: with its cursor atomic
+//    as a buffer atomic); above its 288 bins (m > 288 * 32768), or with
+//    BSDB_D13_VARIANT=2, the round-1 sort kernel k_pass1_d13 (up to 1024
+//    partitions).  Every other value of the variable means 0.
+//  * 8 / 12 / 16-byte keys: k_pass1_d13e, a key's 16-byte window from its
+//    aligned start; BSDB_NO_FIXED_WINDOW=1 sends them to the var-len kernel
+//    instead (A/B switch for measurements).
+//  * variable-length keys and every other fixed length up to 32 B (as k * L
+//    offsets): k_pass1_vare.  (Fixed keys over 32 B: a 128-key group would
+//    overflow its LDS stage.)
+//  * none: a frontend other than 0, fixed keys of 0 or over 32 B, more bins
+//    than the kernel holds.
+// seed0: the kernels with the seed folded at compile time.
+Pass1Sel pass1_select(const bsdb_ctx *c, bool var, uint32_t key_len, bool seed0, uint64_t m) {
+    const uint32_t nparts = (uint32_t)((m + PART_BUCKETS - 1) / PART_BUCKETS);
+    const Pass1Sel none{nullptr, 0, 0, false, false, (uint32_t)PART_SHIFT, nparts, 0};
+    const Pass1Sel sort{k_pass1_d13<512>, 512, 512 * P1_KEYS_PER_THREAD, false, true, (uint32_t)PART_SHIFT, nparts, 0};
+    const bool sort_fits = nparts <= 1024;
+    if (c->frontend != 0) return none;
+    const bool k13 = !var && key_len == 13;
+    const bool window = k13 || (!var && (key_len == 8 || key_len == 12 || key_len == 16) && !getenv("BSDB_NO_FIXED_WINDOW"));
+    if (window) {
+        if (k13 && c->d13_variant == 2) return sort_fits ? sort : none;
+        D13Kernel k = key_len == 8    ? (seed0 ? k_pass1_d13e<0, true, 8> : k_pass1_d13e<0, false, 8>)
+                      : key_len == 12 ? (seed0 ? k_pass1_d13e<0, true, 12> : k_pass1_d13e<0, false, 12>)
+                      : key_len == 16 ? (seed0 ? k_pass1_d13e<0, true, 16> : k_pass1_d13e<0, false, 16>)
+                      : c->d13_variant == 13 ? (seed0 ? k_pass1_d13e<13, true> : k_pass1_d13e<13>)
+                                             : (seed0 ? k_pass1_d13e<0, true> : k_pass1_d13e<0>);
+        Pass1Sel sel{k, D13E_NT, D13E_TILE, true, true, 0, 0, 0};
+        if (binned_layout(sel, D13E_MAXP, D13E_BIN_IDS, m)) return sel;
+        return k13 && sort_fits ? sort : none;
+    }
+    if (!var && (key_len == 0 || key_len > 32)) return none;
+    D13Kernel k = var ? (seed0 ? k_pass1_vare<false, true> : k_pass1_vare<false>)
+                      : (seed0 ? k_pass1_vare<true, true> : k_pass1_vare<true>);
+    Pass1Sel sel{k, VARE_NT, VARE_TILE, true, false, 0, 0, 0};
+    return binned_layout(sel, VARE_MAXP, VARE_BIN_IDS, m) ? sel : none;
 }
 
 // Region capacities: a bin's expected share per region copy plus 8 sigma and
@@ -581,12 +582,12 @@ bool binned_layout(const D13Sel &sel, uint64_t m, uint32_t &shift, uint32_t &nbi
 // cap raises the overflow flag and the chunk is recounted with direct
 // atomics.  Layout of the id buffer: [nmain][P][cap], then the tail kernel's
 // [ntail][P][cap_tail].
-PartPlan plan_partitions(const bsdb_ctx *c, uint64_t chunk, uint64_t m, bool d13, const D13Sel &sel) {
+PartPlan plan_partitions(const bsdb_ctx *c, uint64_t chunk, uint64_t m, const Pass1Sel &sel) {
     PartPlan p{};
-    const bool binned = d13 && sel.binned;
-    p.bin_shift = PART_SHIFT;
-    p.nparts = (uint32_t)((m + PART_BUCKETS - 1) / PART_BUCKETS);
-    if (binned) binned_layout(sel, m, p.bin_shift, p.nparts, p.capb);
+    const bool d13 = sel.k != nullptr, binned = sel.binned;
+    p.bin_shift = sel.bin_shift;
+    p.nparts = sel.nparts;
+    p.capb = sel.capb;
     const double frac = std::min(1.0, (double)(1ULL << p.bin_shift) / (double)m);
     p.nmain = binned ? (uint32_t)c->d13_copies : NCOPY;
     const double e = (double)chunk * frac / p.nmain;
@@ -637,8 +638,6 @@ int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t
     if (per_cu < 1) return BSDB_OK;  // every workgroup must be resident
     const size_t sync_bytes = FU_SYNC_U64 * sizeof(uint64_t);
     const size_t ring_bytes = (size_t)FU_SLOTS * FU_SLOT_BYTES;
-    int variant = 0;
-    if (const char *v = getenv("BSDB_FU_VARIANT")) variant = atoi(v);
     int rc = grow(&c->fu_ring, &c->fu_ring_bytes, ring_bytes + sync_bytes);
     if (rc) return rc;
     FusedArgs fa{};
@@ -656,12 +655,7 @@ int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t
     ++c->fu_launches;
     {
         ProfScope ps(c, s, 0, nsuper * per);
-        // BSDB_FU_VARIANT (profiling, fused_kernels.hip): 1, 2, 4 results invalid, 8 phase stamps
-        if (variant == 1) k_hist13_fused<true, 1><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-        else if (variant == 2) k_hist13_fused<true, 2><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-        else if (variant == 4) k_hist13_fused<true, 4><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-        else if (variant == 8) k_hist13_fused<true, 8><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-        else if (seed == 0 && !getenv("BSDB_NO_SEED0"))
+        if (seed == 0 && !getenv("BSDB_NO_SEED0"))
             k_hist13_fused<true><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
         else
             k_hist13_fused<false><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
@@ -728,28 +722,16 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     uint64_t chunk = c->chunk_keys ? c->chunk_keys : DEFAULT_CHUNK_KEYS;
     chunk = std::max<uint64_t>(P1_TILE, chunk / P1_TILE * P1_TILE);
     chunk = std::min<uint64_t>(chunk, (n + P1_TILE - 1) / P1_TILE * P1_TILE);
-    // the persistent kernels: 13-byte keys and variable-length keys
-    D13Sel sel = d13_select(c, var, key_len, seed == 0 && !getenv("BSDB_NO_SEED0"));  // (A/B switch for measurements)
-    uint32_t bsh = 0, nb = 0, cb = 0;
-    const bool windowed = !var && windowed_len(key_len);  // k_pass1_d13e (13 B, or 8 / 12 / 16 B)
-    const bool fixed_other = !var && !windowed;
-    // (fixed keys over 32 B: a 128-key group would overflow the var-len
-    // kernel's LDS stage, so they stay on the one-tile-per-workgroup kernels)
-    bool d13 = c->frontend == 0 && !(fixed_other && (key_len == 0 || key_len > 32)) &&
-               (sel.binned ? binned_layout(sel, m, bsh, nb, cb) : nparts <= sel.maxp);
-    if (!d13 && !var && key_len == 13 && c->frontend == 0 && sel.binned) {
-        // more bins than the binned kernel holds (m > 288 * 32768): the
-        // round-1 persistent sort kernel (up to 1024 partitions)
-        sel = D13Sel{k_pass1_d13<512>, 512, 512 * P1_KEYS_PER_THREAD, 1024, false, 0};
-        d13 = nparts <= sel.maxp;
-    }
-    const bool pipe_pl = pipe_wanted(c) && d13 && windowed && sel.binned;
+    // the persistent kernel, if any (BSDB_NO_SEED0: A/B switch for measurements)
+    const Pass1Sel sel = pass1_select(c, var, key_len, seed == 0 && !getenv("BSDB_NO_SEED0"), m);
+    const bool d13 = sel.k != nullptr;
+    const bool pipe_pl = pipe_wanted(c) && sel.windowed && sel.binned;
     if (pipe_pl && !c->chunk_keys) {
         // equal chunks of whole tiles: pass 2 of each beside pass 1 of the next
         const uint64_t nch = c->pipe_chunks ? c->pipe_chunks : 8;
         chunk = std::max<uint64_t>(sel.tile, ((n + nch - 1) / nch + sel.tile - 1) / sel.tile * sel.tile);
     }
-    PartPlan pp = plan_partitions(c, chunk, m, d13, sel);
+    PartPlan pp = plan_partitions(c, chunk, m, sel);
     // the id buffers take at most half of the device memory left (workspace
     // included); the 13-byte kernel addresses one region set (P segments)
     // with 32-bit offsets
@@ -759,7 +741,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     while (chunk > 2 * P1_TILE && (pp.ids_elems() * sizeof(uint16_t) > budget ||
                                    (uint64_t)pp.nparts * pp.cap >= (1ULL << 32))) {
         chunk = std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE);
-        pp = plan_partitions(c, chunk, m, d13, sel);
+        pp = plan_partitions(c, chunk, m, sel);
     }
     const uint32_t R = pp.nmain + pp.ntail;
     // Pass 2 of chunk i overlapped with pass 1 of chunk i + 1 (13-byte
@@ -768,7 +750,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     // KiB of LDS, pass 1's 146 KiB: one per CU each, so the two launches
     // split the chip); pass 2 on the context's second stream.  The first
     // pass 1 and the last pass 2 get the whole chip.
-    const bool pipe = pipe_wanted(c) && d13 && windowed && sel.binned && n > chunk;
+    const bool pipe = pipe_pl && n > chunk;
     const int nbuf = pipe ? 2 : 1;
     const size_t ids_per_buf = pp.ids_elems(), cur_per_buf = (size_t)pp.nparts * R;
     int rc = grow(&c->ids, &c->ids_bytes, nbuf * ids_per_buf * sizeof(uint16_t));
@@ -835,7 +817,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
         {
             ProfScope ps(c, s, 0, nk);
             const uint64_t tiles = (nk + P1_TILE - 1) / P1_TILE;
-            if (d13 && (var || fixed_other)) {
+            if (d13 && !sel.windowed) {
                 // full tiles to the persistent kernel, the rest (< 1 of its
                 // tiles) to the generic kernel, in the tail regions
                 const uint64_t nfast = nk / sel.tile;
@@ -974,7 +956,6 @@ int bsdb_open(int device, bsdb_ctx **out) {
     if (const char *v = std::getenv("BSDB_PIPE")) c->pipe = std::atoi(v) ? 1 : 0;
     if (const char *v = std::getenv("BSDB_PIPE_CHUNKS")) c->pipe_chunks = std::strtoull(v, nullptr, 10);
     if (const char *v = std::getenv("BSDB_PIPE_P2CUS")) c->pipe_cus = (uint32_t)std::atoi(v);
-    if (const char *v = std::getenv("BSDB_D13_THREADS")) c->d13_threads = std::atoi(v) == 256 ? 256 : 512;
     if (const char *v = std::getenv("BSDB_D13_COPIES")) {
         const int k = std::atoi(v);
         c->d13_copies = (k == 16 || k == 32 || k == 64) ? k : 8;

@@ -90,13 +90,8 @@ __device__ __forceinline__ void fu_decide(uint64_t *p, uint64_t v) {
                                                __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// VAR 0 is production.  Profiling only (results invalid unless noted): bit 0
-// no consumer (no polls, loads or table adds), bit 1 no run stores, bit 2 no
-// waits on the round counters, bit 3 per-wave phase cycles (s_memtime)
-// over counts[8 (16 p + wave) + k] (nothing else added).
-template <bool SEED0, int VAR = 0>
+template <bool SEED0>
 __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
-    constexpr bool NO_CONS = VAR & 1, NO_STORE = VAR & 2, NO_WAIT = VAR & 4, STAMP = VAR & 8;
     constexpr int NT = FU_NT, TILE = FU_TILE, L = 13, CAPB = FU_CAPB;
     const uint64_t seed = SEED0 ? 0ull : a.seed;
     __shared__ uint32_t table[FU_TCAP / 2];
@@ -220,8 +215,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
         return ovf;
     };
 
-    // STAMP: wait, write-out, hash, consume, drain+barrier, iterations, spinning (in wait), store drain (in drain+barrier)
-    uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ts = 0;
     // ---- consume: my bins of round y from every producer's region
     // thread t reads producer t >> 2, chunks (t & 3) + 4 i of my bin
     const uint32_t cprod = (uint32_t)tid >> 2, csub = (uint32_t)tid & 3;
@@ -259,8 +252,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
         const uint32_t expect = (uint32_t)(FU_OWNERS * (y / SLOTS + 1));
         uint64_t v = poll_sum();
         uint32_t spins = 0;
-        uint64_t t_spin = 0;
-        if constexpr (STAMP) t_spin = __builtin_amdgcn_s_memtime();
         while (!dead && (uint32_t)v != expect) {
             __builtin_amdgcn_s_sleep(2);
             if (++spins > FU_SPIN_MAX || fu_load_relaxed(abort_w) != 0) {
@@ -271,7 +262,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
             issue_poll(y);
             v = poll_sum();
         }
-        if constexpr (STAMP) st[6] += __builtin_amdgcn_s_memtime() - t_spin;
         any_ovf |= (v >> 32) != 0;
     };
     auto load_hdr = [&](uint64_t y) {
@@ -315,13 +305,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
     // ---- one iteration h: round h hashed (h < H), round h - 1 published,
     // round h - lag consumed, round h - lag + 1's headers read, round
     // h - lag + 2 polled
-    auto stamp = [&](int k) {
-        if constexpr (STAMP) {
-            const uint64_t now = __builtin_amdgcn_s_memtime();
-            st[k] += now - ts;
-            ts = now;
-        }
-    };
     uint32_t h3_next = 0;
     auto iter = [&](auto qc, uint64_t h, uint64_t next_t) {
         constexpr int QA = decltype(qc)::value;  // 0: quarters 0, 1; 2: quarters 2, 3; -1: drain (no hash)
@@ -330,18 +313,14 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
         const uint32_t h3 = h3_next;  // h % 3
         h3_next = h3 == 2 ? 0 : h3 + 1;
         if (h + 1 < H && tid < FU_OWNERS) cnt[h3_next][tid] = 0;
-        if (!NO_CONS) {
-            if (yc >= 0) consume_load((uint64_t)yc);  // headers read last iteration
-            if (yh >= 0 && (uint64_t)yh < H) {
-                if (!NO_WAIT) wait_round((uint64_t)yh);
-                load_hdr((uint64_t)yh);
-            }
-            if (yp >= 0 && (uint64_t)yp < H) issue_poll((uint64_t)yp);
+        if (yc >= 0) consume_load((uint64_t)yc);  // headers read last iteration
+        if (yh >= 0 && (uint64_t)yh < H) {
+            wait_round((uint64_t)yh);
+            load_hdr((uint64_t)yh);
         }
-        stamp(0);
-        if (!NO_STORE && h >= 1 && h - 1 < H) write_out(h - 1);
+        if (yp >= 0 && (uint64_t)yp < H) issue_poll((uint64_t)yp);
+        if (h >= 1 && h - 1 < H) write_out(h - 1);
         asm volatile("" ::: "memory");  // the stores stay older than the prefetch below
-        stamp(1);
         if constexpr (QA >= 0) {
             uint32_t *const cn = cnt[h3];
             const uint32_t bsel = (uint32_t)(h & 1);
@@ -350,19 +329,14 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
             hash_q(std::integral_constant<int, QA + 1>{}, cn, bsel);
             load_q(std::integral_constant<int, QA + 1>{}, next_t);
         }
-        stamp(2);
-        if (!NO_CONS && yc >= 0 && !dead) consume_add((uint64_t)yc);
-        stamp(3);
+        if (yc >= 0 && !dead) consume_add((uint64_t)yc);
         // drain this wave's stores (everything but the 8 prefetch loads):
         // the signal below covers them
         if constexpr (QA >= 0)
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (STAMP) st[7] += __builtin_amdgcn_s_memtime() - ts;
         __syncthreads();
-        stamp(4);
-        ++st[5];
         if (h < H) {
             const bool ovf = plan_round(cnt[h3]);
             if (ovf) ovf_round[h & 1] = 1;
@@ -382,7 +356,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
     load_q(std::integral_constant<int, 2>{}, t0);
     load_q(std::integral_constant<int, 3>{}, t0);
     __syncthreads();  // table, counters zeroed
-    if constexpr (STAMP) ts = __builtin_amdgcn_s_memtime();
     for (uint64_t k = 0; k < a.nsuper; ++k) {
         // past the last super-tile the loads re-read tile t0 (unconditional)
         const uint64_t nt = k + 1 < a.nsuper ? (k + 1) * FU_OWNERS + p : t0;
@@ -390,12 +363,6 @@ __global__ __launch_bounds__(FU_NT, 1) void k_hist13_fused(FusedArgs a) {
         iter(std::integral_constant<int, 2>{}, 2 * k + 1, nt);
     }
     for (uint64_t h = H; h < H + LAG; ++h) iter(std::integral_constant<int, -1>{}, h, t0);
-    if constexpr (STAMP) {
-        // over counts[] (results invalid): cycles / 16 per phase, iterations
-        if (l == 0)
-            for (int k = 0; k < 8; ++k) a.counts[((size_t)p * FU_NW + w) * 8 + k] = (uint32_t)(k != 5 ? st[k] >> 4 : st[k]);
-        return;
-    }
 
     // ---- end: my table's total against the ids I added, then the agreement
     uint64_t tsum = 0;

@@ -46,27 +46,11 @@ constexpr int GS_PER_CU = GOV_PER_CU;
 constexpr int GS_CMAX = GOV_CMAX;    // keys per bucket solved in LDS (expected ~1500, sigma ~39)
 constexpr int GS_NVMAX = GS_CMAX + GS_CMAX / 8;   // > vertex_offset span of GS_CMAX keys (1872)
 constexpr int GS_TINY = 12;      // brute-force buckets (only in sets of < ~1500 keys)
-#ifndef GOV_GJ_REG
-// the heavy system's Gauss-Jordan in registers (gauss_jordan_reg): needs the
-// VGPRs of two waves per SIMD (256-thread workgroups, two per CU)
-#define GOV_GJ_REG (GOV_THREADS <= 256)
-#endif
-#ifndef GOV_GJ_REG_HW
-#define GOV_GJ_REG_HW 6  // the widest heavy rows (64-bit words a plane) the register form takes
-#endif
 #ifndef GOV_GJ_FOLLOW
 #define GOV_GJ_FOLLOW 1  // panel form: recorded pivots a following wave takes at once (2, 4, 8: slower)
 #endif
-#ifndef GOV_GJ_B2
-#define GOV_GJ_B2 4  // panel form: a panel's columns a row's trailing update takes at once (a power of two)
-#endif
 #ifndef GOV_GJ_SLEEP
 #define GOV_GJ_SLEEP 1   // panel form: s_sleep of a following wave that waits for the leader
-#endif
-#ifndef GOV_GJ_PANEL
-// the heavy system's Gauss-Jordan by 64-column panels, pivots found by the
-// leader wave (gauss_jordan_panel): bit-identical; C2 solve -10 %
-#define GOV_GJ_PANEL 1
 #endif
 // LDS words of the panel form's scratch for n unknowns: the waves' pivot
 // slots (5 words each), a panel's recorded pivots (4 words a column), the
@@ -75,24 +59,6 @@ constexpr int GS_TINY = 12;      // brute-force buckets (only in sets of < ~1500
 __host__ __device__ constexpr size_t gj_panel_words(uint32_t n) {
     return (size_t)(GOV_THREADS / 64) * 5 + (size_t)4 * 64 + (size_t)2 * 32 * 9;  // slots, pinfo, the pair table
 }
-#ifndef GOV_GREEDY_BRANCHFREE
-#define GOV_GREEDY_BRANCHFREE 1  // greedy steps without exec-mask branches (dead-word stores)
-#endif
-#ifndef GOV_BACK_NOBARRIER
-#define GOV_BACK_NOBARRIER 0  // peeled edges solved as their vertices become final, no barrier per round (back -23 %, the solve +0.3 %: more spills; not kept)
-#endif
-#ifndef GOV_SWEEP_INNER
-#define GOV_SWEEP_INNER 1  // SCC reach sweeps: rounds of reads and marks per barrier (2: half the barriers, sweeps -13 %, the solve unchanged; not kept)
-#endif
-#ifndef GOV_CLOSURE_BRANCHFREE
-#define GOV_CLOSURE_BRANCHFREE 1  // FVS closure batches without exec-mask branches (dead-word stores)
-#endif
-#ifndef GOV_BFS_BRANCHFREE
-#define GOV_BFS_BRANCHFREE 1  // BFS rounds without exec-mask branches (dead-word stores)
-#endif
-#ifndef GOV_GREEDY_ROUNDS
-#define GOV_GREEDY_ROUNDS 1  // greedy: a chunk's overlapping lanes decided in rounds (0: one at a time)
-#endif
 #ifndef GOV_GREEDY_CHUNK
 #define GOV_GREEDY_CHUNK 64  // core edges the greedy orientation takes a step (wave 0)
 #endif
@@ -643,15 +609,12 @@ __device__ __forceinline__ void gf3_add(uint64_t &x1, uint64_t &x2, uint64_t y1,
 // singletons, the FVS closure, the Gauss-Jordan leader) hold up their whole
 // workgroup: that wave takes the highest issue priority while it works, so
 // the co-resident waves of the CU's other solver workgroup (throughput work)
-// do not delay it at its SIMD.  GOV_PRIO=0 builds the form without.
-#ifndef GOV_PRIO
-#define GOV_PRIO 1
-#endif
+// do not delay it at its SIMD.
 __device__ __forceinline__ void crit_on() {
-    if (GOV_PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
 }
 __device__ __forceinline__ void crit_off() {
-    if (GOV_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 }
 
 // Phase counters; P = false (production) compiles them away, so the
@@ -877,12 +840,10 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
     // earlier lane of the chunk touches ("independent") decides at once
     // (nothing before it in the chunk changes its vertices' ownership or
     // counts, and it touches no vertex of an earlier lane); the others
-    // resolve in edge order in registers after reloading ownership and
-    // counts (which then hold every independent lane's effect -- an
-    // independent lane shares no vertex with an earlier one, so those are
-    // all earlier lanes): lane j's choice and vertices are broadcast, the
-    // later lanes clear the chosen vertex and take j's decrements.
-    // Together, the sequential outcome.
+    // decide in rounds of the same kind (below) after reloading ownership
+    // and counts.  Together, the sequential outcome.  (The others resolved
+    // one at a time in registers, each lane's choice broadcast to the later
+    // ones: not kept.)
     if (tid < 64) {
         crit_on();  // (the one wave working: first at its SIMD)
         uint32_t *firstl = L.xe;  // (dead after peeling) lowest lane of the chunk touching a vertex
@@ -898,10 +859,9 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
         };
         // a chunk's edges and vertices are read one chunk ahead (neither
         // changes here), so a chunk starts at its ownership reads
-#if GOV_GREEDY_BRANCHFREE
-        // (every lane reads -- a lane past the edges reads edge 0 -- and the
+        // (no exec-mask branches in a step: every lane reads -- a lane past the edges reads edge 0 -- and the
         // lanes with nothing to do aim their atomics and stores at a dead
-        // word of their own: no exec-mask branches in a step)
+        // word of their own)
         uint32_t *const dead = L.hbin;  // (dead until the FVS selection, which clears them)
         int16_t *const dead16 = reinterpret_cast<int16_t *>(dead);
         auto chunk_edges = [&](uint32_t k, bool &a, uint32_t &u0, uint32_t &u1, uint32_t &u2) {
@@ -912,17 +872,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
             u2 = L.e[3 * kc + 2];
             a = k < cnt && ro < 0;
         };
-#else
-        auto chunk_edges = [&](uint32_t k, bool &a, uint32_t &u0, uint32_t &u1, uint32_t &u2) {
-            a = k < cnt && L.round_of[k] < 0;
-            u0 = u1 = u2 = 0;
-            if (a) {
-                u0 = L.e[3 * k];
-                u1 = L.e[3 * k + 1];
-                u2 = L.e[3 * k + 2];
-            }
-        };
-#endif
         bool nact;
         uint32_t n0, n1, n2;
         // GOV_GREEDY_CHUNK edges a step (lanes above it idle): fewer lanes
@@ -939,7 +888,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
             bool f0 = false, f1 = false, f2 = false;
             const uint32_t me = lane_tag | tid;
             lane_tag -= 64;
-#if GOV_GREEDY_BRANCHFREE
             // decide: the lane's choice (or none) and its decrements, stores
             // aimed at the dead words unless `on`
             auto decide = [&](bool on, int &ch) {
@@ -984,7 +932,11 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 if (on) chosen = c;
             }
             uint64_t todo = __builtin_amdgcn_ballot_w64(ovl);
-            while (todo) {  // (wave-uniform) the overlapping lanes in rounds, as below
+            // the overlapping lanes in rounds: a lane no earlier lane still
+            // to decide shares a vertex with sees, after the previous rounds,
+            // every earlier effect on its vertices, so it decides now (the
+            // lanes of a round touch disjoint vertices); the rest wait
+            while (todo) {  // (wave-uniform)
                 const bool pend = ((todo >> tid) & 1ULL) != 0;
                 const uint32_t me2 = lane_tag | tid;
                 lane_tag -= 64;
@@ -998,106 +950,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 __builtin_amdgcn_wave_barrier();
             }
             (void)chosen;
-#else
-            if (act) {
-                f0 = L.vowner[v0] < 0;
-                f1 = L.vowner[v1] < 0;
-                f2 = L.vowner[v2] < 0;
-                c0 = ccnt[v0];
-                c1 = ccnt[v1];
-                c2 = ccnt[v2];
-                atomicMin(&firstl[v0], me);
-                atomicMin(&firstl[v1], me);
-                atomicMin(&firstl[v2], me);
-            }
-            __builtin_amdgcn_wave_barrier();
-            const bool ovl = act && (firstl[v0] < me || firstl[v1] < me || firstl[v2] < me);
-            int chosen = -1;
-            if (act && !ovl) {
-                chosen = pick(f0, f1, f2, c0, c1, c2, v0, v1, v2);
-                if (chosen >= 0) {
-                    L.vowner[chosen] = (int16_t)k;
-                    L.hinge[k] = (int16_t)chosen;
-                }
-                atomicSub(&ccnt[v0], 1u);
-                atomicSub(&ccnt[v1], 1u);
-                atomicSub(&ccnt[v2], 1u);
-            }
-            uint64_t todo = __builtin_amdgcn_ballot_w64(ovl);
-#if GOV_GREEDY_ROUNDS
-            // the overlapping lanes in rounds: a lane no earlier lane still
-            // to decide shares a vertex with sees, after the previous rounds,
-            // every earlier effect on its vertices, so it decides now (the
-            // lanes of a round touch disjoint vertices); the rest wait
-            while (todo) {  // (wave-uniform)
-                const bool pend = ((todo >> tid) & 1ULL) != 0;
-                const uint32_t me2 = lane_tag | tid;
-                lane_tag -= 64;
-                if (pend) {
-                    atomicMin(&firstl[v0], me2);
-                    atomicMin(&firstl[v1], me2);
-                    atomicMin(&firstl[v2], me2);
-                }
-                __builtin_amdgcn_wave_barrier();
-                const bool wait = pend && (firstl[v0] < me2 || firstl[v1] < me2 || firstl[v2] < me2);
-                if (pend && !wait) {
-                    f0 = L.vowner[v0] < 0;
-                    f1 = L.vowner[v1] < 0;
-                    f2 = L.vowner[v2] < 0;
-                    c0 = ccnt[v0];
-                    c1 = ccnt[v1];
-                    c2 = ccnt[v2];
-                    chosen = pick(f0, f1, f2, c0, c1, c2, v0, v1, v2);
-                    if (chosen >= 0) {
-                        L.vowner[chosen] = (int16_t)k;
-                        L.hinge[k] = (int16_t)chosen;
-                    }
-                    atomicSub(&ccnt[v0], 1u);
-                    atomicSub(&ccnt[v1], 1u);
-                    atomicSub(&ccnt[v2], 1u);
-                }
-                todo = __builtin_amdgcn_ballot_w64(wait);
-                __builtin_amdgcn_wave_barrier();
-            }
-#else
-            if (todo) {  // (wave-uniform)
-                __builtin_amdgcn_wave_barrier();
-                if (ovl) {  // the independent lanes' choices and decrements (all earlier, see above)
-                    f0 = L.vowner[v0] < 0;
-                    f1 = L.vowner[v1] < 0;
-                    f2 = L.vowner[v2] < 0;
-                    c0 = ccnt[v0];
-                    c1 = ccnt[v1];
-                    c2 = ccnt[v2];
-                }
-                while (todo) {
-                    const uint32_t j = (uint32_t)__builtin_ctzll(todo);
-                    todo &= todo - 1;
-                    if (tid == j) chosen = pick(f0, f1, f2, c0, c1, c2, v0, v1, v2);
-                    const int c = __builtin_amdgcn_readlane(chosen, j);
-                    const uint32_t w0 = __builtin_amdgcn_readlane(v0, j), w1 = __builtin_amdgcn_readlane(v1, j),
-                                   w2 = __builtin_amdgcn_readlane(v2, j);
-                    if (c >= 0) {
-                        f0 = f0 && v0 != (uint32_t)c;
-                        f1 = f1 && v1 != (uint32_t)c;
-                        f2 = f2 && v2 != (uint32_t)c;
-                    }
-                    c0 -= (uint32_t)(v0 == w0) + (uint32_t)(v0 == w1) + (uint32_t)(v0 == w2);
-                    c1 -= (uint32_t)(v1 == w0) + (uint32_t)(v1 == w1) + (uint32_t)(v1 == w2);
-                    c2 -= (uint32_t)(v2 == w0) + (uint32_t)(v2 == w1) + (uint32_t)(v2 == w2);
-                }
-                if (ovl) {
-                    if (chosen >= 0) {
-                        L.vowner[chosen] = (int16_t)k;
-                        L.hinge[k] = (int16_t)chosen;
-                    }
-                    atomicSub(&ccnt[v0], 1u);
-                    atomicSub(&ccnt[v1], 1u);
-                    atomicSub(&ccnt[v2], 1u);
-                }
-            }
-#endif
-#endif
             __builtin_amdgcn_wave_barrier();
         }
         // the counts' words become the BFS's stamps
@@ -1158,7 +1010,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 const uint32_t ei = lane / 3, vi = lane - 3 * ei;
                 const uint32_t me = lane_tag | lane;
                 lane_tag -= 64;
-#if GOV_BFS_BRANCHFREE
                 // every lane reads (a lane past the chunk reads its last
                 // edge) and the lanes past it aim their atomic and stores at
                 // a dead word of their own: no exec-mask branches in a round
@@ -1168,17 +1019,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 const uint32_t sn = seen[v];
                 const int o = L.vowner[v];
                 atomicMin(act ? &first_lane[v] : &dead[lane], me);
-#else
-                int k = 0, o = -1;
-                uint32_t v = 0, sn = 0;
-                if (act) {
-                    k = queue[qh + ei];
-                    v = L.e[3 * k + vi];
-                    sn = seen[v];
-                    o = L.vowner[v];
-                    atomicMin(&first_lane[v], me);
-                }
-#endif
                 __builtin_amdgcn_wave_barrier();
                 // (the root's iteration without the queue read and the
                 // atomics, duplicates compared in registers: BFS +2 %, not kept)
@@ -1187,7 +1027,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 const uint32_t F = fb ? (uint32_t)__builtin_ctzll(fb) : 64u;
                 const bool take = valid && lane < F;  // (o >= 0 below F)
                 const uint64_t tb = __builtin_amdgcn_ballot_w64(take);
-#if GOV_BFS_BRANCHFREE
                 {
                     const uint32_t pos = qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(tb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tb, 0u));
                     int16_t *const dead16 = reinterpret_cast<int16_t *>(dead);
@@ -1195,14 +1034,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                     *(take ? &bfs_prev[o] : &dead16[lane]) = (int16_t)k;
                     *(take ? &queue[pos] : &dead16[64 + lane]) = (int16_t)o;
                 }
-#else
-                if (valid && lane <= F) seen[v] = epoch;
-                if (take) {
-                    const uint32_t pos = qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(tb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tb, 0u));
-                    bfs_prev[o] = (int16_t)k;
-                    queue[pos] = (int16_t)o;
-                }
-#endif
                 qt += (uint32_t)__builtin_popcountll(tb);
                 qh += ch;
                 npops += ch;
@@ -1353,14 +1184,13 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
 #pragma unroll
             for (int i = 0; i < 3; ++i) dk[j][i] = core ? (int)L.dep[3 * k + i] : -1;
         }
-        // GOV_SWEEP_INNER rounds a barrier: a round's reads see this
-        // thread's earlier marks and whatever other threads' marks have
-        // landed, so a barrier covers up to that many levels; the marks only
-        // grow, so the fixpoint (F, B) is the same, and a barrier interval
-        // in which no thread marks anything ends the sweeps
+        // One round of reads and marks a barrier: the marks only grow, so
+        // the fixpoint (F, B) does not depend on the order they land in, and
+        // a barrier interval in which no thread marks anything ends the
+        // sweeps.  (Two rounds a barrier: half the barriers, sweeps -13 %,
+        // the solve unchanged; not kept.)
         for (;;) {
-          int ch = 0;
-          for (uint32_t inner = 0; inner < GOV_SWEEP_INNER; ++inner) {
+            int ch = 0;
             uint32_t fk[KPT], fw[KPT][3];
 #pragma unroll
             for (uint32_t j = 0; j < KPT; ++j) {
@@ -1387,7 +1217,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                     ch = 1;
                 }
             }
-          }
             pc.add(GP_N_SCC_SWEEPS, 1);
             if (!__syncthreads_or(ch)) break;
         }
@@ -1712,119 +1541,8 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
             }
             return gj_tail(n, X);
         };
-        // The heavy system's Gauss-Jordan with each row in its own thread's
-        // registers (n <= GS_THREADS rows of H words a plane; the solver's
-        // 256-thread form has the VGPRs for it, GOV_GJ_REG): per column,
-        // every wave's lowest candidate row for the next pivot publishes its
-        // index and words in the wave's slot (double-buffered by column
-        // parity); after the column's one barrier every thread reads the
-        // waves' bids, takes the lowest row -- the pivot the LDS form's
-        // atomicMin picks -- reads its words from that wave's slot and
-        // eliminates in registers: two LDS round trips a column instead of the
-        // LDS form's chain of ~6.  Same pivots, same reduced
-        // rows (written back at the end), same tail.
-        auto gauss_jordan_reg = [&](uint32_t n, auto hw, auto &&X, uint64_t *slots) -> bool {
-            constexpr uint32_t H = decltype(hw)::value;
-            constexpr uint32_t NW = GS_THREADS / 64, SW = 2 * H + 1;  // a slot: the row index, then its words
-            int16_t *piv = L.a0;
-            uint8_t *used_m = L.b1;
-            const uint32_t rr = tid, lane = tid & 63, wv = tid >> 6;
-            const bool mine = rr < n;
-            uint64_t r1[H], r2[H];
-#pragma unroll
-            for (uint32_t w = 0; w < H; ++w) {
-                r1[w] = mine ? X(rr, w, 0) : 0;
-                r2[w] = mine ? X(rr, w, 1) : 0;
-            }
-            bool used = false;
-            uint32_t nfree = 0;
-            auto publish = [&](uint32_t c, uint32_t par) {  // the wave's lowest candidate for column c
-                bool cand = false;
-                if (mine && !used && c < n) {
-                    uint64_t t = 0;
-#pragma unroll
-                    for (uint32_t w = 0; w < H; ++w)
-                        if (w == (c >> 6)) t = r1[w] | r2[w];
-                    cand = ((t >> (c & 63)) & 1ULL) != 0;
-                }
-                const uint64_t bal = __builtin_amdgcn_ballot_w64(cand);
-                uint64_t *sl = slots + (size_t)(par * NW + wv) * SW;
-                if (!bal) {
-                    if (lane == 0) sl[0] = ~0ULL;
-                } else if (lane == (uint32_t)__builtin_ctzll(bal)) {
-                    sl[0] = rr;
-#pragma unroll
-                    for (uint32_t w = 0; w < H; ++w) {
-                        sl[1 + 2 * w] = r1[w];
-                        sl[2 + 2 * w] = r2[w];
-                    }
-                }
-            };
-            __syncthreads();  // (every row read before the slots, which may share its words, are written)
-            publish(0, 0);
-            __syncthreads();
-            for (uint32_t cc = 0; cc < n; ++cc) {
-                const uint32_t par = cc & 1;
-                uint64_t best = ~0ULL;
-                uint32_t bw = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < NW; ++w) {
-                    const uint64_t b = slots[(size_t)(par * NW + w) * SW];
-                    if (b < best) {
-                        best = b;
-                        bw = w;
-                    }
-                }
-                if (best == ~0ULL) {  // a free column (uniform): x_cc = 0
-                    if (tid == 0) piv[cc] = -1;
-                    ++nfree;
-                    publish(cc + 1, par ^ 1u);
-                    __syncthreads();
-                    continue;
-                }
-                const uint64_t *ps = slots + (size_t)(par * NW + bw) * SW;
-                uint64_t q1[H], q2[H];
-#pragma unroll
-                for (uint32_t w = 0; w < H; ++w) {
-                    q1[w] = ps[1 + 2 * w];
-                    q2[w] = ps[2 + 2 * w];
-                }
-                const uint32_t wc = cc >> 6;
-                const uint64_t bit = 1ULL << (cc & 63);
-                uint64_t pq2 = 0, f1 = 0, f2 = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < H; ++w)
-                    if (w == wc) {
-                        pq2 = q2[w];
-                        f1 = r1[w] & bit;
-                        f2 = r2[w] & bit;
-                    }
-                const bool two = (pq2 & bit) != 0;  // pivot coefficient 2: its row normalised = planes swapped
-                if (tid == 0) piv[cc] = (int16_t)best;
-                if (rr == (uint32_t)best) {
-                    used = true;
-                } else if (mine && (f1 | f2)) {
-                    const bool sw = (f1 != 0) != two;  // subtract cf * (normalised pivot row)
-#pragma unroll
-                    for (uint32_t w = 0; w < H; ++w)
-                        if (w >= wc) gf3_add(r1[w], r2[w], sw ? q2[w] : q1[w], sw ? q1[w] : q2[w]);
-                }
-                publish(cc + 1, par ^ 1u);
-                __syncthreads();
-            }
-            if (mine) {
-#pragma unroll
-                for (uint32_t w = 0; w < H; ++w) {
-                    X(rr, w, 0) = r1[w];
-                    X(rr, w, 1) = r2[w];
-                }
-                used_m[rr] = used ? 1 : 0;
-            }
-            if (tid == 0) L.nfree = nfree;
-            __syncthreads();
-            return gj_tail(n, X);
-        };
-        // The heavy system's Gauss-Jordan by 64-column panels (GOV_GJ_PANEL).
+        // The heavy system's Gauss-Jordan by 64-column panels: bit-identical to
+        // gauss_jordan; C2 solve -10 %.
         // Per panel (one word of every row), a row per thread holds in
         // registers its panel word and its multiplier word M over the
         // panel's pivots (row now = row at the panel's start + sum_j M[j]
@@ -2181,7 +1899,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                         ++nbatch;
                         const uint32_t nb = min(64u, qt - qh);
                         uint32_t x0 = 0, x1 = 0, myl = 0;
-#if GOV_CLOSURE_BRANCHFREE
                         // (every lane reads -- a lane past the batch reads its
                         // last member -- and the lanes with nothing to do aim
                         // their atomics and stores at a dead word of their own)
@@ -2201,20 +1918,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                             // while it waited in the queue: its level is 0)
                             myl = pp >= 0x100u ? 1u : lp + 1;
                         }
-#else
-                        if (lane < nb) {
-                            const uint32_t p = (uint32_t)queue[qh + lane];
-                            for (int t = 0; t < 3; ++t) {
-                                const int d = idep[3 * p + t];
-                                if (d >= 0) atomicSub(&indeg[d], 1u);
-                            }
-                            x0 = roff[p];
-                            x1 = roff[p + 1];
-                            // (a heavy member's lvl may have been raised
-                            // while it waited in the queue: its level is 0)
-                            myl = pend[p] >= 0x100u ? 1u : lvl[p] + 1;
-                        }
-#endif
                         // the batch's dependents, one per lane per step; the
                         // members they make ready are appended in lane order
                         // by ballot (the ready closure, the levels and so the
@@ -2227,7 +1930,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                         // lanes by a ballot prefix sum, 64 a step: selection
                         // 3.52e6 -> 3.61e6 cycles, not kept -- a batch's
                         // members have few dependents each)
-#if GOV_CLOSURE_BRANCHFREE
                         for (uint32_t x = x0;; ++x) {
                             const bool act = x < x1;
                             if (__builtin_amdgcn_ballot_w64(act) == 0) break;
@@ -2239,23 +1941,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                             *(ready ? &queue[pos] : &dead16[64 + lane]) = (int16_t)i;
                             qt += (uint32_t)__builtin_popcountll(rm);
                         }
-#else
-                        for (uint32_t x = x0;; ++x) {
-                            const bool act = x < x1;
-                            if (__builtin_amdgcn_ballot_w64(act) == 0) break;
-                            bool ready = false;
-                            uint32_t i = 0;
-                            if (act) {
-                                i = (uint32_t)rev(x);
-                                atomicMax(&lvl[i], myl);
-                                ready = atomicSub(&pend[i], 1u) == 1u;  // its last slot
-                            }
-                            const uint64_t rm = __builtin_amdgcn_ballot_w64(ready);
-                            if (ready)
-                                queue[qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u))] = (int16_t)i;
-                            qt += (uint32_t)__builtin_popcountll(rm);
-                        }
-#endif
                         qh += nb;
                         __builtin_amdgcn_wave_barrier();
                     }
@@ -2289,13 +1974,9 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 // score: a member many others wait on and that waits on many
                 // breaks the most cycles).  Against open dependents alone:
                 // heavy set 223 -> 204 per block, C2 524 -> 537 M keys/s
-                // (`profiles/r4/pick_key_ab/`; GOV_PICK_KEY=0 builds that)
+                // (`profiles/r4/pick_key_ab/`)
                 auto pick_key = [&](uint32_t i) -> uint32_t {
-#if defined(GOV_PICK_KEY) && GOV_PICK_KEY == 0
-                    return indeg[i];
-#else
                     return indeg[i] * (pend[i] & 0xFFu);
-#endif
                 };
                 auto make_heavy = [&](uint32_t i, uint32_t j, uint32_t slot) {
                     pend[i] += 0x100u;
@@ -2536,7 +2217,7 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 // (LDS state only: the following waves poll the leader's
                 // progress word, which a global slab -- SolveBig -- would put
                 // behind the vector L1)
-                const bool panel = GOV_GJ_PANEL && !std::is_same<Lds, SolveBig>::value && nH <= (uint32_t)GS_THREADS &&
+                const bool panel = !std::is_same<Lds, SolveBig>::value && nH <= (uint32_t)GS_THREADS &&
                                    hs_lds && (size_t)2 * HW * nH + pscr <= Lds::HS_WORDS;
                 uint64_t *const hsb = L.hs();
                 auto HSL = [&](uint32_t rr, uint32_t w, uint32_t q) -> uint64_t & { return hsb[(2 * w + q) * nH + rr]; };
@@ -2581,23 +2262,8 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
                 }
                 __syncthreads();
                 // (rows in X: words < 12 CMAX, below the forms)
-                // the register form when the heavy rows are in LDS, one per
-                // thread, with room past them for the wave slots
-                constexpr uint32_t NWV = GS_THREADS / 64;
-                const bool reg = GOV_GJ_REG && hs_lds && nH <= (uint32_t)GS_THREADS && HW <= GOV_GJ_REG_HW &&
-                                 (size_t)2 * HW * nH + (size_t)2 * NWV * (2 * HW + 1) <= Lds::HS_WORDS;
                 bool hok;
-                if (reg) {
-                    uint64_t *slots = hsb + (size_t)2 * HW * nH;
-                    switch (HW) {
-                        case 1: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, 1>{}, HSL, slots); break;
-                        case 2: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, 2>{}, HSL, slots); break;
-                        case 3: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, 3>{}, HSL, slots); break;
-                        case 4: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, GOV_GJ_REG_HW < 4 ? 1 : 4>{}, HSL, slots); break;
-                        case 5: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, GOV_GJ_REG_HW < 5 ? 1 : 5>{}, HSL, slots); break;
-                        default: hok = gauss_jordan_reg(nH, std::integral_constant<uint32_t, GOV_GJ_REG_HW < 6 ? 1 : FW>{}, HSL, slots); break;
-                    }
-                } else if (panel) {
+                if (panel) {
                     hok = gauss_jordan_panel(nH, HSL, hsb + (size_t)2 * HW * nH);
                 } else {
                     hok = hs_lds ? gauss_jordan(nH, HSL) : gauss_jordan(nH, X);
@@ -2765,52 +2431,8 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
     if (!uni(L.flag)) return false;
 
     // ---- 4. peeled edges, last round first
-#if GOV_BACK_NOBARRIER
-    // An edge's value needs only its other vertices' final values (hinges of
-    // edges peeled in later rounds, core hinges, or free vertices = 0), so
-    // no barrier per round: a peeled edge's hinge is marked pending, and each
-    // wave retries its lanes' pending edges until they are solved, reading
-    // the other waves' results as they land (LDS, no caching).  The later
-    // rounds' edges are always ready, so every retry makes progress; the
-    // values are those of the rounds in order.
-    {
-        constexpr uint8_t PEND = 0x80u;
-        for (uint32_t k = tid; k < cnt; k += GS_THREADS)
-            if (L.round_of[k] >= 0) L.xval[L.hinge[k]] = PEND;
-        __syncthreads();
-        volatile uint8_t *xv = L.xval;
-        constexpr uint32_t KPT = (Lds::CMAX + GS_THREADS - 1) / GS_THREADS;
-        uint32_t todo = 0;  // bit j: edge tid + j * GS_THREADS still to solve
-        for (uint32_t j = 0; j < KPT && tid + j * GS_THREADS < cnt; ++j)
-            if (L.round_of[tid + j * GS_THREADS] >= 0) todo |= 1u << j;
-        static_assert(KPT <= 32, "edges a thread");
-        while (__builtin_amdgcn_ballot_w64(todo != 0)) {  // (the wave's own loop)
-            for (uint32_t j = 0; j < KPT; ++j) {
-                if (!((todo >> j) & 1u)) continue;
-                const uint32_t k = tid + j * GS_THREADS;
-                const uint32_t hg = (uint32_t)L.hinge[k];
-                uint32_t s = 0, coef = 0, h = 3;
-                bool ready = true;
-                for (int i = 0; i < 3; ++i) {
-                    const uint32_t v = L.e[3 * k + i];
-                    if (v == hg) {
-                        ++coef;
-                        if (h == 3) h = (uint32_t)i;
-                    } else {
-                        const uint32_t x = xv[v];
-                        ready = ready && !(x & PEND);
-                        s += x;
-                    }
-                }
-                if (!ready) continue;
-                const uint32_t rhs = (h + 6 - s) % 3;
-                xv[hg] = (uint8_t)(coef == 1 ? rhs : (2 * rhs) % 3);
-                todo &= ~(1u << j);
-            }
-        }
-        __syncthreads();
-    }
-#else
+    // (Each edge solved as its vertices become final, with no barrier per
+    // round: back -23 %, the solve +0.3 % -- more spills; not kept.)
     for (int rr = rounds - 1; rr >= 0; --rr) {
         for (uint32_t k = tid; k < cnt; k += GS_THREADS) {
             if (L.round_of[k] != rr) continue;
@@ -2826,8 +2448,6 @@ __device__ __forceinline__ bool try_seed(Lds &L, const ulonglong2 *sig, uint32_t
         }
         __syncthreads();
     }
-#endif
-    (void)rounds;
     pc.lap(GP_BACK);
     return true;
 }

@@ -433,9 +433,10 @@ __global__ __launch_bounds__(P1_THREADS, 4) void k_pass1(P1Args a) {
 constexpr int D13_Q = 4;                          // keys per quarter
 constexpr int D13_NQ = P1_KEYS_PER_THREAD / D13_Q;  // quarters per tile
 
-// Kept as the reference point for k_pass1_d13e (BSDB_D13_VARIANT=2): the
-// round-1 epilogue, with its loads made unconditional and the epilogue run at
-// raised wave priority (the workgroup's critical path).
+// The production kernel above k_pass1_d13e's 288 bins, and its reference
+// point (BSDB_D13_VARIANT=2); only NT = 512 is built.  The round-1 epilogue,
+// with its loads made unconditional and the epilogue run at raised wave
+// priority (the workgroup's critical path).
 template <int NT>
 __global__ __launch_bounds__(NT, 4) void k_pass1_d13(P1Args a, uint64_t ntiles) {
     constexpr int TILE = NT * P1_KEYS_PER_THREAD;
@@ -593,19 +594,15 @@ constexpr int D13E_BIN_IDS = 36864;  // ids per bin buffer: nparts * capb (72 Ki
 constexpr int D13E_MAXP = 288;       // bins (capb >= 128 ids: tile share 57 +- 7.5 at 288 bins)
 constexpr uint16_t ID_PAD = 0xFFFF;                       // not a local id (ids are < 2^15)
 
-// VARIANT 0 is production.  Profiling only (results invalid): 1 = hash and
-// bins, no cursor atomics and no write-out; 4 = per-wave phase cycles
-// (s_memtime) written over counts[8*wave ..] (tools/stamp_probe_e.py);
-// 12 = everything but the hash: the same loads, bins, cursor atomics and
-// write-out with a 2-instruction stand-in bucket (uniform over [0, m) for
-// random key bytes) -- what pass 1's memory traffic alone costs.
-// 13 (results valid) = the cursor atomic as a range-checked buffer atomic:
+// VARIANT 0 is production.  13 (the same results) = the cursor atomic as a
+// range-checked buffer atomic:
 // the lanes without a partition send nothing to memory (0.15 ms of pass 1 at
 // C4, inside the run-to-run spread: not the default).
 // L: the key length, 13 or an aligned 8 / 12 / 16 (the same design; the
 // 16-byte window of a key then starts at the key itself).
 template <int VARIANT, bool SEED0 = false, int L = 13>
 __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t ntiles) {
+    static_assert(VARIANT == 0 || VARIANT == 13, "0: production; 13: the buffer-atomic cursor");
     static_assert(L == 13 || L == 8 || L == 12 || L == 16, "key lengths of the windowed kernel");
     // SEED0: the seed is 0 (every BSDBWriter build, CBHS:209): the hash's
     // seed terms fold at compile time
@@ -674,9 +671,7 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         uint32_t b[D13_Q], r[D13_Q];
 #pragma unroll
         for (int j = 0; j < D13_Q; ++j) {
-            if constexpr (VARIANT == 12)
-                b[j] = __umulhi(S[q][j].x ^ S[q][j].z, mult >> 1);
-            else if constexpr (L == 13)
+            if constexpr (L == 13)
                 b[j] = spooky13_bucket(S[q][j].x, S[q][j].y, S[q][j].z, S[q][j].w, sh, seed, mult);
             else
                 b[j] = spooky_fix_bucket<L>(S[q][j].x, S[q][j].y, S[q][j].z, S[q][j].w, seed, mult);
@@ -749,17 +744,6 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     __syncthreads();  // cnt zeroed
     uint32_t cur = 0;
     bool have_prev = false;
-    constexpr bool STAMP = VARIANT == 4;  // diagnostic: phase cycles over counts[]
-    uint64_t st_h = 0, st_w = 0, st_b = 0, st_o = 0, ts = 0, st_t0 = 0;
-    uint32_t st_n = 0;
-    auto stamp = [&](uint64_t &acc) {
-        if (STAMP) {
-            const uint64_t now = __builtin_amdgcn_s_memtime();
-            acc += now - ts;
-            ts = now;
-        }
-    };
-    if (STAMP) st_t0 = ts = __builtin_amdgcn_s_memtime();
     for (uint64_t t = t0; t < ntiles; t += G, cur ^= 1) {
         hash_q(0, cur);
         load_q(0, t + G);
@@ -768,13 +752,9 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         hash_q(2, cur);
         load_q(2, t + G);
         hash_q(3, cur);
-        stamp(st_h);
-        if (have_prev && VARIANT != 1) write_out(cur ^ 1);
+        if (have_prev) write_out(cur ^ 1);
         load_q(3, t + G);
-        stamp(st_w);
         __syncthreads();  // bins[cur] complete; bins[cur ^ 1] written out
-        stamp(st_b);
-        ++st_n;
         // owners: count, reserve the whole chunks, re-arm at the remainder
         const uint32_t copy = (uint32_t)(t & (a.ncopy - 1));
         c8_prev = 0;
@@ -797,27 +777,17 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         if constexpr (BUF_ATOMIC)
             b_prev = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(
                 (int)c8_prev, cur_rsrc, my_p < P ? (copy * P + my_p) * 4u : cur_bytes + 4u * l, 0, 0);
-        else if (VARIANT != 1)
+        else
             b_prev = atomicAdd(my_p < P ? a.cursor + copy * P + my_p : a.scratch + P1_SCRATCH_WG + blockIdx.x * 1024 + tid,
                                c8_prev);
         copy_prev = copy;
         have_prev = true;
-        stamp(st_o);
     }
-    if (STAMP && l == 0) {
-        const uint64_t wg = (uint64_t)blockIdx.x * NW + w;
-        a.counts[8 * wg + 0] = (uint32_t)(st_h >> 4);
-        a.counts[8 * wg + 1] = (uint32_t)(st_w >> 4);
-        a.counts[8 * wg + 2] = (uint32_t)(st_b >> 4);
-        a.counts[8 * wg + 3] = (uint32_t)(st_o >> 4);
-        a.counts[8 * wg + 4] = (uint32_t)((__builtin_amdgcn_s_memtime() - st_t0) >> 4);
-        a.counts[8 * wg + 5] = st_n;
-    }
-    if (have_prev && VARIANT != 1) write_out(cur ^ 1);
+    if (have_prev) write_out(cur ^ 1);
     // the last two remainders of my_p: the one carried to the start of
     // bins[cur] (its tile's successor never came) and the last tile's, moved
     // by write_out to the start of bins[cur ^ 1]: one run padded to 8
-    if (have_prev && VARIANT != 1 && my_p < P) {
+    if (have_prev && my_p < P) {
         uint16_t *const bc = &bins[cur][my_p * CAPB];
         const uint32_t r0 = cnt[cur][my_p], r1 = rm_prev;  // (<= 7 each)
         for (uint32_t e = 0; e < r1; ++e) bc[r0 + e] = bins[cur ^ 1][my_p * CAPB + e];
@@ -875,9 +845,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
            (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, l);
 }
 
-// VARIANT 0 is production.  Profiling only (results invalid): 1 = no cursor
-// atomics and no write-out; 4 = phase cycles (s_memtime) over counts[8*wave
-// ..].
 // k_pass1_vare's general-length paths (keys over 64 B, groups over the stage),
 // out of line: the unrolled hot loop then carries one copy of each.
 __device__ __forceinline__ uint64_t vare_sig0_lds(const uint32_t *stage, uint32_t o, uint32_t len,
@@ -904,7 +871,7 @@ __device__ __forceinline__ uint64_t vare_sig0_global(const uint32_t *src, uint64
 
 // FIXED: keys of a.key_len bytes each, no offsets array (key k at k * L):
 // the same kernel serves every fixed length but 13 (k_pass1_d13e).
-template <int VARIANT, bool FIXED, bool SEED0 = false>
+template <bool FIXED, bool SEED0 = false>
 __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t ntiles) {
     const uint64_t seed = SEED0 ? 0ull : a.seed;  // (as k_pass1_d13e)
     constexpr int NT = VARE_NT, NW = VARE_NW, TILE = VARE_TILE, NG = VARE_NG;
@@ -929,15 +896,6 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
     const uint32_t PPW = (P + NW - 1) / NW;  // <= 18
     const bool owner = (uint32_t)l < PPW && (uint32_t)w * PPW + l < P;
     const uint32_t my_p = owner ? (uint32_t)w * PPW + l : P;
-    constexpr bool STAMP = VARIANT == 4;
-    uint64_t st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = 0, st_t0 = 0;
-    auto stamp = [&](int ph) __attribute__((always_inline)) {
-        if (STAMP) {
-            const uint64_t now = __builtin_amdgcn_s_memtime();
-            st_acc[ph] += now - st_last;
-            st_last = now;
-        }
-    };
 
     // Range bounds of this wave's NG groups of a tile: lane 2g holds
     // off[first key of group g], lane 2g+1 off[its last key + 1].  Past the
@@ -1027,28 +985,10 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
     // B); a branch runs whenever ANY lane takes it, so the caller sorts a
     // group's keys short-first: chain 0 then holds only keys < 16 B (no mix,
     // 5 dwords) unless the group has fewer than 64 of them.
-    // VARIANT 5 (profiling, results invalid): every lane reads a conflict-free
-    // address instead of its key's.  VARIANT 6: 8-byte aligned ds_read_b64
-    // reads, the odd-dword start selected in registers.
     auto read_key = [&](uint32_t b, auto nc, uint32_t *d) __attribute__((always_inline)) {
         constexpr int N = decltype(nc)::value;
-        if (VARIANT == 6) {
-            const uint64_t *q = reinterpret_cast<const uint64_t *>(stage) + (b >> 1);
-            const bool odd = b & 1;
-            uint32_t x[N + 1 + (N & 1)];
 #pragma unroll
-            for (int i = 0; i < (N + 2) / 2; ++i) {
-                const uint64_t v = q[i];
-                x[2 * i] = (uint32_t)v;
-                x[2 * i + 1] = (uint32_t)(v >> 32);
-            }
-#pragma unroll
-            for (int i = 0; i < N; ++i) d[i] = odd ? x[i + 1] : x[i];
-        } else {
-            const uint32_t bb = VARIANT == 5 ? (uint32_t)l * 17 : b;
-#pragma unroll
-            for (int i = 0; i < N; ++i) d[i] = stage[bb + i];
-        }
+        for (int i = 0; i < N; ++i) d[i] = stage[b + i];
     };
     auto sig0_staged = [&](uint32_t o, uint32_t len) __attribute__((always_inline)) {
         const uint32_t b = o >> 2, sh = (o & 3) * 8;
@@ -1142,21 +1082,16 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
     auto step = [&](auto jc, uint64_t tt) __attribute__((always_inline)) {
         constexpr int j = decltype(jc)::value;
         constexpr int r = j & 1;
-        stamp(5);
         stage_group(r);
-        stamp(0);
         const uint64_t pos = O01[r].x, lo = Blo[r];
         const uint32_t la = (uint32_t)(O01[r].y - O01[r].x), lb = (uint32_t)(O2[r] - O01[r].y), nvec = Bn[r];
         if (j + 2 < NG) issue_B(r, bnd_cur, j + 2, tt);
         else issue_B(r, bnd_next, j + 2 - NG, tt + G);
-        stamp(1);
         __builtin_amdgcn_wave_barrier();
         hash_group(pos, la, lb, lo, nvec);
         __builtin_amdgcn_wave_barrier();  // this stage is refilled by the next group
-        stamp(2);
     };
 
-    if (STAMP) st_t0 = st_last = __builtin_amdgcn_s_memtime();
     bnd_cur = load_bounds(t0);
     issue_B(0, bnd_cur, 0, t0);
     issue_B(1, bnd_cur, 1, t0);
@@ -1174,7 +1109,6 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
         static_assert(NG == 8, "step calls");
         flush_inserts();
         __syncthreads();  // bins complete
-        stamp(3);
         // owners: count, pad to a multiple of 8, re-arm, reserve; every lane
         // issues the atomic (a lane without a bin adds 0 to a scratch word of
         // its own: same-word lanes are serialised at the memory side)
@@ -1187,9 +1121,7 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
             c8 = c > CAPB ? 0 : (c + 7) & ~7u;
             for (uint32_t e = c; e < c8; ++e) bins[my_p * CAPB + e] = ID_PAD;
         }
-        uint32_t base = 0;
-        if (VARIANT != 1)
-            base = atomicAdd(my_p < P ? a.cursor + copy * P + my_p : a.scratch + P1_SCRATCH_WG + blockIdx.x * 1024 + tid, c8);
+        const uint32_t base = atomicAdd(my_p < P ? a.cursor + copy * P + my_p : a.scratch + P1_SCRATCH_WG + blockIdx.x * 1024 + tid, c8);
         // while the atomics fly: step 0 of the next tile, up to its rank
         // atomics (other counters; its ids reach the bins after the barrier
         // below).  Past the last tile it hashes tile t0 again, to no effect.
@@ -1197,16 +1129,8 @@ __global__ __launch_bounds__(VARE_NT, 4) void k_pass1_vare(P1Args a, uint64_t nt
         bnd_cur = bnd_next;
         bnd_next = load_bounds(t + 2 * G);
         step(std::integral_constant<int, 0>{}, t + G);
-        stamp(2);
-        if (VARIANT != 1) write_out(c8, base, copy);
-        stamp(4);
+        write_out(c8, base, copy);
         __syncthreads();  // bins written out and counters re-armed
-        stamp(3);
-    }
-    if (STAMP && l == 0) {
-        const uint64_t wg = (uint64_t)blockIdx.x * NW + w;
-        for (int i = 0; i < 6; ++i) a.counts[8 * wg + i] = (uint32_t)(st_acc[i] >> 4);
-        a.counts[8 * wg + 6] = (uint32_t)((__builtin_amdgcn_s_memtime() - st_t0) >> 4);
     }
     if (ovf) atomicOr(a.overflow, 1u);
 }

@@ -53,8 +53,7 @@ def main():
     ctx.set_frontend(0)
     counts.zero_()
     ctx.histogram_var(blob, off, m, counts=counts)
-    if os.environ.get("BSDB_D13_VARIANT", "0") == "0":  # profiling variants give invalid counts
-        assert int(counts.sum(dtype=torch.int64)) == n
+    assert int(counts.sum(dtype=torch.int64)) == n
     print(json.dumps(res))
 
 
