@@ -57,9 +57,10 @@ struct bsdb_ctx {
     int hist_mode = 0;
     int frontend = 0;  // 13-byte keys: 0 auto (pipelined), 1 LDS-staged, 2 direct per-tile
     int num_cus = 256;
-    int d13_variant = 0;  // 13-byte keys' pass-1 kernel (BSDB_D13_VARIANT, see pass1_select): the same results under each
+    int d13_variant = 13;  // 13-byte keys' pass-1 kernel (BSDB_D13_VARIANT, see pass1_select): the same results under each
     int d13_copies = 8;     // region copies of the binned 13-byte kernel (BSDB_D13_COPIES=8|16|32)
-    uint64_t chunk_keys = 0;
+    uint64_t chunk_keys = 0;  // keys per pass-1 launch (0 = default)
+    uint64_t span_max = 0;    // pass-1 launches per pass 2, at most (0 = default; BSDB_SPAN_MAX)
     int fused = -1;  // 13-byte keys, single-pass kernel: -1 = what mode 0 picks (BSDB_FUSED), 0 off, 1 on
     int pipe = -1;   // pass 2 of a chunk beside pass 1 of the next: -1 default, 0 off, 1 on (BSDB_PIPE)
     uint64_t pipe_chunks = 0;  // chunks of the pipelined histogram (0 = default; BSDB_PIPE_CHUNKS)
@@ -164,7 +165,13 @@ static void comm_destroy(bsdb_ctx *c);  // capi_comm.hip
 
 namespace {
 
-constexpr uint64_t DEFAULT_CHUNK_KEYS = 1ULL << 32;  // measured: 2^32 286 G keys/s, 2^33 284, one launch (13.2e9) 266
+// Keys per pass-1 LAUNCH (bsdb_set_chunk_keys).  Measured: 2^32 286 G keys/s,
+// 2^33 284, one launch (13.2e9) 266.  Pass 2 runs once per SPAN of up to
+// MAX_SPAN_LAUNCHES launches (histogram_impl), not once per launch.
+constexpr uint64_t DEFAULT_CHUNK_KEYS = 1ULL << 32;
+// k_pass2_plan (one workgroup) scans P * (J * nmain + ntail) items: 19 368 at
+// C4's 269 bins, 8 copies and J = 8
+constexpr uint64_t MAX_SPAN_LAUNCHES = 8;
 
 // BSDB_DEBUG=1: every failing HIP call behind an EIO is reported on stderr
 // with its source line (the return code alone does not say which call failed)
@@ -538,10 +545,11 @@ bool binned_layout(Pass1Sel &sel, uint32_t maxp, uint32_t bin_ids, uint64_t m) {
 }
 
 // The one place that chooses pass 1's kernel (two-pass path, m buckets):
-//  * 13-byte keys: k_pass1_d13e (BSDB_D13_VARIANT=13: with its cursor atomic
-//    as a buffer atomic); above its 288 bins (m > 288 * 32768), or with
-//    BSDB_D13_VARIANT=2, the round-1 sort kernel k_pass1_d13 (up to 1024
-//    partitions).  Every other value of the variable means 0.
+//  * 13-byte keys: k_pass1_d13e with its cursor atomic as a buffer atomic
+//    (VARIANT 13, the default; BSDB_D13_VARIANT=0: as a flat atomic); above
+//    its 288 bins (m > 288 * 32768), or with BSDB_D13_VARIANT=2, the round-1
+//    sort kernel k_pass1_d13 (up to 1024 partitions).  Every other value of
+//    the variable means 0.
 //  * 8 / 12 / 16-byte keys: k_pass1_d13e, a key's 16-byte window from its
 //    aligned start; BSDB_NO_FIXED_WINDOW=1 sends them to the var-len kernel
 //    instead (A/B switch for measurements).
@@ -731,6 +739,12 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
         const uint64_t nch = c->pipe_chunks ? c->pipe_chunks : 8;
         chunk = std::max<uint64_t>(sel.tile, ((n + nch - 1) / nch + sel.tile - 1) / sel.tile * sel.tile);
     }
+    // several launches of a persistent kernel: whole tiles of it each, so
+    // that only a span's last launch leaves keys to the tail kernel
+    auto whole_tiles = [&](uint64_t ch) {
+        return d13 && !pipe_pl && ch < n && ch >= sel.tile ? ch / sel.tile * sel.tile : ch;
+    };
+    chunk = whole_tiles(chunk);
     PartPlan pp = plan_partitions(c, chunk, m, sel);
     // the id buffers take at most half of the device memory left (workspace
     // included); the 13-byte kernel addresses one region set (P segments)
@@ -740,10 +754,29 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     const size_t budget = (free_b + c->ids_bytes) / 2 / (pipe_pl ? 2 : 1);
     while (chunk > 2 * P1_TILE && (pp.ids_elems() * sizeof(uint16_t) > budget ||
                                    (uint64_t)pp.nparts * pp.cap >= (1ULL << 32))) {
-        chunk = std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE);
+        chunk = whole_tiles(std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE));
         pp = plan_partitions(c, chunk, m, sel);
     }
-    const uint32_t R = pp.nmain + pp.ntail;
+    // A span: J consecutive pass-1 launches of chunk keys, each into a region
+    // set of its own, then ONE pass 2 over all of them (its workgroups flush
+    // their LDS tables once per span, not once per launch).  Layout of a
+    // span's ids: [J][nmain][P][cap], then the tail regions; of its cursors:
+    // [J][nmain][P], then the tail's -- to pass 2 one launch with J * nmain
+    // main regions.  As many launches as the memory budget above holds, at
+    // most MAX_SPAN_LAUNCHES (k_pass2_plan's item count), c->span_max if set.
+    // A persistent kernel's launches must be whole tiles of it: every launch
+    // but the span's last then runs entirely in that kernel, and the span
+    // has one set of tail regions.  (The one-tile-per-workgroup kernels have
+    // no tail: any launch length, a multiple of P1_TILE.)
+    const size_t set_elems = (size_t)pp.nparts * pp.nmain * pp.cap;               // ids of one launch's main regions
+    const size_t tail_elems = (size_t)pp.nparts * pp.ntail * pp.cap_tail;         // ids of the tail regions
+    uint64_t J = 1;
+    if (!pipe_pl && n > chunk && (!d13 || chunk % sel.tile == 0)) {
+        const uint64_t jmax = c->span_max ? c->span_max : MAX_SPAN_LAUNCHES;
+        J = std::min<uint64_t>({(n + chunk - 1) / chunk, jmax, MAX_SPAN_LAUNCHES});
+        while (J > 1 && (J * set_elems + tail_elems) * sizeof(uint16_t) > budget) --J;
+    }
+    const uint32_t R = (uint32_t)J * pp.nmain + pp.ntail;
     // Pass 2 of chunk i overlapped with pass 1 of chunk i + 1 (13-byte
     // windowed keys, several chunks): two id buffers; pass 1 on the caller's
     // stream over all CUs but the ones pass 2 keeps (its workgroups hold 128
@@ -752,7 +785,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     // pass 1 and the last pass 2 get the whole chip.
     const bool pipe = pipe_pl && n > chunk;
     const int nbuf = pipe ? 2 : 1;
-    const size_t ids_per_buf = pp.ids_elems(), cur_per_buf = (size_t)pp.nparts * R;
+    const size_t ids_per_buf = J * set_elems + tail_elems, cur_per_buf = (size_t)pp.nparts * R;
     int rc = grow(&c->ids, &c->ids_bytes, nbuf * ids_per_buf * sizeof(uint16_t));
     if (rc) return rc;
     rc = grow((void **)&c->cursor, &c->cursor_bytes,
@@ -787,66 +820,91 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     L0.bshift = PART_SHIFT - pp.bin_shift;
     L0.num_buckets = m;
     L0.counts = counts;
-    uint64_t i = 0;
-    for (uint64_t k0 = 0; k0 < n; k0 += chunk, ++i) {
-        const uint64_t nk = std::min(chunk, n - k0);
-        const bool first = k0 == 0, last = k0 + nk >= n;
+    uint64_t i = 0;  // launch of the call
+    for (uint64_t s0 = 0; s0 < n; s0 += J * chunk) {
+        // a span: keys [s0, s0 + ns) in jn launches (pipelined: one)
+        const uint64_t ns = std::min(J * chunk, n - s0), jn = (ns + chunk - 1) / chunk;
+        const bool last = s0 + ns >= n;
         const uint32_t b = pipe ? (uint32_t)(i & 1) : 0;
         // buffer b's ids, cursors, pass-2 plan and overflow flag
-        P1Args ac = a;
-        ac.ids = (uint16_t *)c->ids + b * ids_per_buf;
-        ac.cursor = c->cursor + b * cur_per_buf;
-        ac.overflow = c->overflow + 4 * b;
+        P1Args as = a;
+        as.ids = (uint16_t *)c->ids + b * ids_per_buf;
+        as.cursor = c->cursor + b * cur_per_buf;
+        as.overflow = c->overflow + 4 * b;
         uint64_t *pref = c->p2_pref + b * (cur_per_buf + 1);
+        // the tail regions follow the main regions of the jn launches
+        uint16_t *const tail_ids = as.ids + jn * set_elems;
+        uint32_t *const tail_cur = as.cursor + jn * pp.nmain * pp.nparts;
         P2Layout L = L0;
-        L.ids = ac.ids;
-        L.cursor = ac.cursor;
-        L.overflow = ac.overflow;
-        ac.n = nk;
+        L.ids = as.ids;
+        L.cursor = as.cursor;
+        L.overflow = as.overflow;
+        L.nmain = (uint32_t)jn * pp.nmain;
+        const size_t cur_span = (size_t)pp.nparts * (L.nmain + L.ntail);
+        as.n = ns;
         if (var) {
-            ac.offsets = offsets + k0;
+            as.offsets = offsets + s0;
         } else {
-            ac.keys = keys + k0 * key_len;
-            // a window past the chunk reads the next chunk's bytes (the blob
-            // goes on): only the blob's end limits the persistent kernel
-            ac.blob_bytes = pipe ? blob_bytes - k0 * key_len : nk * key_len;
+            as.keys = keys + s0 * key_len;
+            as.blob_bytes = pipe ? blob_bytes - s0 * key_len : ns * key_len;
         }
         if (pipe && i >= 2) HIP_OK(hipStreamWaitEvent(s, c->pipe_ev[2 + b], 0));  // pass 2 of chunk i - 2 read buffer b
-        HIP_OK(hipMemsetAsync(ac.cursor, 0, sizeof(uint32_t) * cur_per_buf, s));
-        HIP_OK(hipMemsetAsync(ac.overflow, 0, sizeof(uint32_t), s));
-        {
+        HIP_OK(hipMemsetAsync(as.cursor, 0, sizeof(uint32_t) * cur_span, s));
+        HIP_OK(hipMemsetAsync(as.overflow, 0, sizeof(uint32_t), s));
+        for (uint64_t j = 0; j < jn; ++j, ++i) {
+            const uint64_t k0 = s0 + j * chunk, nk = std::min(chunk, n - k0);
+            const bool first = k0 == 0, last_of_span = j + 1 == jn;
+            // launch j's region set
+            P1Args ac = as;
+            ac.ids = as.ids + j * set_elems;
+            ac.cursor = as.cursor + j * pp.nmain * pp.nparts;
+            ac.n = nk;
+            if (var) {
+                ac.offsets = offsets + k0;
+            } else {
+                ac.keys = keys + k0 * key_len;
+                // a window past the launch reads the next launch's bytes (the
+                // blob goes on): only the blob's end limits the persistent
+                // kernel, so a launch of whole tiles leaves no tail.  (A
+                // span's last launch keeps its own length, as a call of one
+                // launch always had.)
+                const bool to_end = pipe || !last_of_span;
+                ac.blob_bytes = to_end ? blob_bytes - k0 * key_len : nk * key_len;
+            }
             ProfScope ps(c, s, 0, nk);
             const uint64_t tiles = (nk + P1_TILE - 1) / P1_TILE;
+            // the keys from `done` on: to the bounds-checked kernel, in the
+            // tail regions
+            auto tail = [&](uint64_t done) {
+                P1Args at = ac;
+                at.n = nk - done;
+                at.ids = tail_ids;
+                at.cursor = tail_cur;
+                at.cap = pp.cap_tail;
+                at.nregions = pp.ntail;
+                if (var) {
+                    at.offsets = ac.offsets + done;
+                    k_pass1<SRC_VAR, EPI_PARTITION, 1, 0><<<(uint32_t)((at.n + P1_TILE - 1) / P1_TILE), P1_THREADS, 0, s>>>(at);
+                } else {
+                    at.keys = ac.keys + done * key_len;
+                    at.blob_bytes = at.n * key_len;
+                    launch_pass1<EPI_PARTITION>(at, false, key_len, (at.n + P1_TILE - 1) / P1_TILE, s, 0);
+                }
+            };
             if (d13 && !sel.windowed) {
                 // full tiles to the persistent kernel, the rest (< 1 of its
-                // tiles) to the generic kernel, in the tail regions
+                // tiles) to the generic kernel
                 const uint64_t nfast = nk / sel.tile;
                 if (nfast) {
                     const uint32_t grid = (uint32_t)std::min<uint64_t>(nfast, pp.grid_d13);
                     sel.k<<<grid, sel.nt, 0, s>>>(ac, nfast);
                 }
-                const uint64_t done = nfast * sel.tile;
-                if (done < nk) {
-                    P1Args at = ac;
-                    at.n = nk - done;
-                    at.ids = ac.ids + (size_t)pp.nmain * pp.nparts * pp.cap;
-                    at.cursor = ac.cursor + (size_t)pp.nmain * pp.nparts;
-                    at.cap = pp.cap_tail;
-                    at.nregions = pp.ntail;
-                    if (var) {
-                        at.offsets = ac.offsets + done;
-                        k_pass1<SRC_VAR, EPI_PARTITION, 1, 0><<<(uint32_t)((at.n + P1_TILE - 1) / P1_TILE), P1_THREADS, 0, s>>>(at);
-                    } else {
-                        at.keys = ac.keys + done * key_len;
-                        at.blob_bytes = at.n * key_len;
-                        launch_pass1<EPI_PARTITION>(at, false, key_len, (at.n + P1_TILE - 1) / P1_TILE, s, 0);
-                    }
-                }
+                if (nfast * sel.tile < nk) tail(nfast * sel.tile);
             } else if (d13) {
                 // full tiles whose 16-byte windows stay inside the readable
                 // blob go to the persistent kernel (a key's window ends 16 - L
                 // bytes past it at most); the rest (< 2 of its tiles) to the
-                // bounds-checked kernel, in the tail regions
+                // bounds-checked kernel
                 const uint64_t dtile = sel.tile, over = 16 - key_len;
                 uint64_t nfast = 0;
                 if (ac.blob_bytes >= over) nfast = std::min(nk / dtile, ((ac.blob_bytes - over) / key_len) / dtile);
@@ -855,18 +913,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
                     if (pipe && !first) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (uint32_t)c->num_cus - p2_cus));
                     sel.k<<<grid, sel.nt, 0, s>>>(ac, nfast);
                 }
-                const uint64_t done = nfast * dtile;
-                if (done < nk) {
-                    P1Args at = ac;
-                    at.keys = ac.keys + done * key_len;
-                    at.n = nk - done;
-                    at.blob_bytes = at.n * key_len;
-                    at.ids = ac.ids + (size_t)pp.nmain * pp.nparts * pp.cap;
-                    at.cursor = ac.cursor + (size_t)pp.nmain * pp.nparts;
-                    at.cap = pp.cap_tail;
-                    at.nregions = pp.ntail;
-                    launch_pass1<EPI_PARTITION>(at, false, key_len, (at.n + P1_TILE - 1) / P1_TILE, s, 0);
-                }
+                if (nfast * dtile < nk) tail(nfast * dtile);
             } else {
                 launch_pass1<EPI_PARTITION>(ac, var, key_len, tiles, s, c->frontend);
             }
@@ -876,15 +923,17 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
             HIP_OK(hipStreamWaitEvent(s2, c->pipe_ev[b], 0));
         }
         {
-            ProfScope ps(c, s2, 1, nk);
+            ProfScope ps(c, s2, 1, ns);
             k_pass2_plan<<<1, SCAN_THREADS, 0, s2>>>(L, pref);
             const uint32_t g2 = pipe && !last ? p2_cus : (uint32_t)c->num_cus;
             k_pass2b<<<g2, P2_THREADS, 0, s2>>>(L, pref);
         }
+        // an overflow anywhere in the span: pass 2 skipped all of it, and the
+        // whole span is recounted
         if (var) {
-            k_overflow_fallback<SRC_VAR, 0><<<1024, P1_THREADS, 0, s2>>>(ac);
+            k_overflow_fallback<SRC_VAR, 0><<<1024, P1_THREADS, 0, s2>>>(as);
         } else {
-            k_overflow_fallback<SRC_FIXED_DIRECT, 0><<<1024, P1_THREADS, 0, s2>>>(ac);
+            k_overflow_fallback<SRC_FIXED_DIRECT, 0><<<1024, P1_THREADS, 0, s2>>>(as);
         }
         if (pipe) HIP_OK(hipEventRecord(c->pipe_ev[2 + b], s2));  // buffer b free again
         if ((rc = launch_status())) return rc;
@@ -952,6 +1001,8 @@ int bsdb_open(int device, bsdb_ctx **out) {
     if (!c) return BSDB_ENOMEM;
     c->device = device;
     if (const char *v = std::getenv("BSDB_D13_VARIANT")) c->d13_variant = std::atoi(v);
+    // measurement aid: pass-1 launches per pass 2, at most (1 = a pass 2 per launch)
+    if (const char *v = std::getenv("BSDB_SPAN_MAX")) c->span_max = std::strtoull(v, nullptr, 10);
     if (const char *v = std::getenv("BSDB_FUSED")) c->fused = std::atoi(v) ? 1 : 0;
     if (const char *v = std::getenv("BSDB_PIPE")) c->pipe = std::atoi(v) ? 1 : 0;
     if (const char *v = std::getenv("BSDB_PIPE_CHUNKS")) c->pipe_chunks = std::strtoull(v, nullptr, 10);

@@ -594,10 +594,11 @@ constexpr int D13E_BIN_IDS = 36864;  // ids per bin buffer: nparts * capb (72 Ki
 constexpr int D13E_MAXP = 288;       // bins (capb >= 128 ids: tile share 57 +- 7.5 at 288 bins)
 constexpr uint16_t ID_PAD = 0xFFFF;                       // not a local id (ids are < 2^15)
 
-// VARIANT 0 is production.  13 (the same results) = the cursor atomic as a
-// range-checked buffer atomic:
-// the lanes without a partition send nothing to memory (0.15 ms of pass 1 at
-// C4, inside the run-to-run spread: not the default).
+// VARIANT 13 (13-byte keys' default) = the cursor atomic as a range-checked
+// buffer atomic: the lanes without a partition send nothing to memory (0.6 GB
+// of WRITE_SIZE per 2^32-key launch and 0.19 ms of a C4 step).
+// VARIANT 0 (the same results; 8 / 12 / 16-byte keys, BSDB_D13_VARIANT=0):
+// a flat atomic, those lanes adding 0 to a scratch word.
 // L: the key length, 13 or an aligned 8 / 12 / 16 (the same design; the
 // 16-byte window of a key then starts at the key itself).
 template <int VARIANT, bool SEED0 = false, int L = 13>

@@ -1,8 +1,10 @@
-"""Verdicts of the pass-1 request A/B (profiles/pass1_requests/).
+"""Verdicts of the pass-1 request A/B and of the pass-2 span A/B (DESIGN §4.1,
+profiles/pass1_requests/, profiles/pass2_span/).
 
 Reads DIR/<name>.jsonl (bench.py result lines of alternated runs, one file
-per library: parent, req_a, req_b, req_c, all) and prints, per library, the
-median / min / max of ms_per_step and of pass 1's kernel time, and whether
+per library: parent, req_a, req_b, req_c or span_a, span_ab, span_c, all,
+final) and prints, per library, the
+median / min / max of ms_per_step and of each pass's kernel time, and whether
 its median gain over the parent exceeds the parent's own max - min spread
 (the bar a change has to clear to stay in the default kernel).
 usage: python tools/pass1_requests_verdict.py DIR [OUT_JSON]"""
@@ -18,9 +20,11 @@ def column(path, get):
 
 def main():
     d = sys.argv[1]
-    fields = {"ms_per_step": lambda r: r["ms_per_step"], "pass1_ms": lambda r: r["kernel_ms_per_step"]["pass1"]}
+    fields = {"ms_per_step": lambda r: r["ms_per_step"], "pass1_ms": lambda r: r["kernel_ms_per_step"]["pass1"],
+              "pass2_ms": lambda r: r["kernel_ms_per_step"]["pass2"]}
     out = {}
-    for name in ("parent", "req_a", "req_b", "req_c", "all"):
+    # profiles/pass1_requests/: req_a, req_b, req_c; profiles/pass2_span/: span_a, span_ab, span_c, final
+    for name in ("parent", "req_a", "req_b", "req_c", "span_a", "span_ab", "span_c", "all", "final"):
         path = os.path.join(d, name + ".jsonl")
         if not os.path.exists(path):
             continue
