@@ -38,6 +38,7 @@
 #include "fused_kernels.hip"
 #include "mph_kernels.hip"
 #include "gov_kernels.hip"
+#include "verify_kernels.hip"
 
 using namespace bsdb;
 
@@ -1988,3 +1989,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_passes.hip"
 #include "capi_builder.hip"
 #include "capi_kv.hip"
+#include "capi_verify.hip"

@@ -122,7 +122,20 @@ SIGNATURES = [
     ("bsdb_kv_records_free", _i, [_vp]),
     ("bsdb_kv_build_index", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, _u32, _i, C.c_char_p, C.c_char_p,
                                  C.POINTER(_vp)]),
+    ("bsdb_dev_verify_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _vp, _u32,
+                                   _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_verify_var", _i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _vp,
+                                 _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_mph_verify_index_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
+    ("bsdb_mph_verify_index_var", _i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
+    ("bsdb_kv_verify_index", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
 ]
+
+BSDB_EVERIFY = -74
+VERIFY_WORDS = 8
+# the report's words in the header's order (out[BSDB_VERIFY_WORDS])
+VERIFY_FIELDS = ("records", "rejected", "in_window", "wrong_addr", "wrong_value", "min_bad_addr", "flags", "windows")
+VERIFY_E_INVALID, VERIFY_INDEX_SIZE, VERIFY_RECORD_COUNT = 1, 2, 4  # bits of "flags"
 
 HIST_AUTO, HIST_PARTITIONED, HIST_ATOMIC = 0, 1, 2
 
@@ -158,6 +171,16 @@ def lib() -> C.CDLL:
 def _check(fn: str, rc: int):
     if rc != BSDB_OK:
         raise BsdbError(fn, rc)
+
+
+def _verify_report(fn: str, rc: int, out) -> dict:
+    """The report of a verify call as a dict (VERIFY_FIELDS + ``ok``): BSDB_OK
+    and BSDB_EVERIFY both return it, every other code raises."""
+    if rc not in (BSDB_OK, BSDB_EVERIFY):
+        raise BsdbError(fn, rc)
+    rep = {k: int(v) for k, v in zip(VERIFY_FIELDS, out)}
+    rep["ok"] = rc == BSDB_OK
+    return rep
 
 
 def num_buckets(n: int) -> int:
@@ -588,6 +611,57 @@ class Context:
             _ptr(value8) if value8 is not None else None, _ptr(value_len) if value_len is not None else None,
             _ptr(index_a) if index_a is not None else None, _stream(stream)))
 
+    # ---- F4: the fused database check on device-resident records
+    @staticmethod
+    def verify_out(device):
+        """A zeroed report for verify_fixed / verify_var ([5] = all ones)."""
+        import torch
+        out = torch.zeros(VERIFY_WORDS, dtype=torch.int64, device=device)
+        out[5] = -1
+        return out
+
+    def _verify_args(self, n, E, values, width, sigbits, start, length, index, index_a, out, stream):
+        return (n, E.numel() - 1, _ptr(E), _ptr(values), width, _ptr(sigbits) if sigbits is not None else None,
+                start, length, _ptr(index), _ptr(index_a) if index_a is not None else None, _ptr(out), _stream(stream))
+
+    @staticmethod
+    def _verify_counters(out):
+        return tuple(int(x) & (2**64 - 1) for x in out[:6].cpu().tolist())
+
+    def verify_fixed(self, keys, key_len: int, n: int, E, values, index, start: int = 0, length: Optional[int] = None,
+                     width: int = 0, sigbits=None, addr=None, addr_base: int = 0, addr_stride: int = 0, first: int = 0,
+                     value8=None, vlen=None, index_a=None, out=None, stream=None):
+        """bsdb_dev_verify_fixed: keys.numel() // key_len records against the
+        slots of ranks [start, start + length) in `index` (and `index_a`).
+        Accumulates into `out` (verify_out()); returns the six counters
+        (records, rejected, in_window, wrong_addr, wrong_value, min_bad_addr)."""
+        count = keys.numel() // key_len
+        if length is None:
+            length = index.numel()
+        if out is None:
+            out = self.verify_out(keys.device)
+        _check("bsdb_dev_verify_fixed", lib().bsdb_dev_verify_fixed(
+            self._h, _ptr(keys), key_len, count, _ptr(addr) if addr is not None else None, addr_base, addr_stride,
+            first, _ptr(value8) if value8 is not None else None, _ptr(vlen) if vlen is not None else None,
+            *self._verify_args(n, E, values, width, sigbits, start, length, index, index_a, out, stream)))
+        return self._verify_counters(out)
+
+    def verify_var(self, blob, offsets, n: int, E, values, index, start: int = 0, length: Optional[int] = None,
+                   width: int = 0, sigbits=None, addr=None, addr_base: int = 0, addr_stride: int = 0, first: int = 0,
+                   value8=None, vlen=None, index_a=None, out=None, stream=None):
+        """bsdb_dev_verify_var: as verify_fixed for a key blob with offsets."""
+        count = offsets.numel() - 1
+        if length is None:
+            length = index.numel()
+        if out is None:
+            out = self.verify_out(offsets.device)
+        _check("bsdb_dev_verify_var", lib().bsdb_dev_verify_var(
+            self._h, _ptr(blob), blob.numel(), _ptr(offsets), count, _ptr(addr) if addr is not None else None,
+            addr_base, addr_stride, first, _ptr(value8) if value8 is not None else None,
+            _ptr(vlen) if vlen is not None else None,
+            *self._verify_args(n, E, values, width, sigbits, start, length, index, index_a, out, stream)))
+        return self._verify_counters(out)
+
     def gen_keys_var(self, first: int, n: int, stream=None):
         """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1])."""
         import torch
@@ -726,6 +800,39 @@ class Mph:
         _check("bsdb_mph_lookup_var", lib().bsdb_mph_lookup_var(
             self._h, blob_np.ctypes.data, off_np.ctypes.data, n, 1 if check else 0, out.ctypes.data))
         return out[:n]
+
+    # ---- F4: the database check (report dict: VERIFY_FIELDS + "ok"; BSDB_EVERIFY does not raise)
+    def verify_index_fixed(self, keys_np, key_len: int, addr_np, index_path: str, index_a_path: Optional[str] = None,
+                           approximate: bool = False, value8_np=None, vlen_np=None, windows: int = 0) -> dict:
+        import numpy as np
+        keys_np = np.ascontiguousarray(keys_np, np.uint8)
+        n = keys_np.size // key_len
+        a, v8, vl = Context._records_args(n, addr_np, value8_np, vlen_np, approximate)
+        out = (C.c_uint64 * VERIFY_WORDS)()
+        rc = lib().bsdb_mph_verify_index_fixed(
+            self._h, keys_np.ctypes.data, key_len, n, a.ctypes.data, _np_ptr(v8), _np_ptr(vl), 1 if approximate else 0,
+            index_path.encode(), index_a_path.encode() if index_a_path else None, windows, out)
+        return _verify_report("bsdb_mph_verify_index_fixed", rc, out)
+
+    def verify_index_var(self, blob_np, off_np, addr_np, index_path: str, index_a_path: Optional[str] = None,
+                         approximate: bool = False, value8_np=None, vlen_np=None, windows: int = 0) -> dict:
+        blob_np, off_np, n = Context._var_host_args(blob_np, off_np)
+        a, v8, vl = Context._records_args(n, addr_np, value8_np, vlen_np, approximate)
+        out = (C.c_uint64 * VERIFY_WORDS)()
+        rc = lib().bsdb_mph_verify_index_var(
+            self._h, blob_np.ctypes.data, off_np.ctypes.data, n, a.ctypes.data, _np_ptr(v8), _np_ptr(vl),
+            1 if approximate else 0, index_path.encode(), index_a_path.encode() if index_a_path else None, windows, out)
+        return _verify_report("bsdb_mph_verify_index_var", rc, out)
+
+    def verify_kv(self, kv_base: str, partitions: int, index_path: str, index_a_path: Optional[str] = None,
+                  approximate: bool = False, fmt: int = 0, block_size: int = 4096, threads: int = 0,
+                  windows: int = 0) -> dict:
+        """bsdb_kv_verify_index: the records from the kv.db partition scan."""
+        out = (C.c_uint64 * VERIFY_WORDS)()
+        rc = lib().bsdb_kv_verify_index(
+            self._h, kv_base.encode(), partitions, fmt, block_size, threads, 1 if approximate else 0,
+            index_path.encode(), index_a_path.encode() if index_a_path else None, windows, out)
+        return _verify_report("bsdb_kv_verify_index", rc, out)
 
     def write_index(self, index_path: str, index_a_path: Optional[str], approximate: bool, pass_cache_bytes: int,
                     feed):

@@ -47,6 +47,14 @@ MAX_KEY_SIZE = 255     # Common.java MAX_KEY_SIZE
 RECORD_HEADER = 3      # Common.java RECORD_HEADER_SIZE
 
 
+class VerifyError(RuntimeError):
+    """``BSDBWriter.verify`` found the database not clean; ``report`` is the dict."""
+
+    def __init__(self, report: dict):
+        super().__init__(f"database verification failed: {report}")
+        self.report = report
+
+
 class BSDBWriter:
     def __init__(self, base_path: str, tmp_dir: Optional[str] = None, checksum_bits: int = 4,
                  pass_cache_size: int = 1 << 30, compact: bool = True, compress: bool = False,
@@ -127,7 +135,27 @@ class BSDBWriter:
                 f.write(f"{k} = {v}\n")
 
     # W:91-97
-    def build(self):
+    def build(self, verify: bool = False):
+        """verify=True: the finished files are checked on the device
+        (``verify``) and a database that is not clean raises."""
+        mph = self._build()
+        if verify:
+            self.verify(mph)
+        return mph
+
+    def verify(self, mph: Mph, windows: int = 0) -> dict:
+        """Builder -v (Builder.java:184-228) batched on the device: every record
+        of the kv.db files this writer wrote goes key -> rank -> index.db slot
+        (-> index_a.db value bytes) in one fused pass (bsdb_kv_verify_index).
+        Returns the report dict (native.VERIFY_FIELDS + ``ok``) of a clean
+        database; raises VerifyError (with ``.report``) otherwise."""
+        rep = mph.verify_kv(os.path.join(self.base, "kv.db"), self.partitions, os.path.join(self.base, "index.db"),
+                            os.path.join(self.base, "index_a.db"), self.approximate, windows=windows)
+        if not rep["ok"]:
+            raise VerifyError(rep)
+        return rep
+
+    def _build(self):
         blob, off, vals = self._records()
         self._addr = self._write_kv(blob, off, vals)
         self._write_config(off, vals)

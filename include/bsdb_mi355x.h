@@ -530,6 +530,77 @@ int bsdb_kv_build_index(bsdb_ctx *ctx, const char *kv_base, int partitions, int 
                         int threads, uint32_t width, int approximate, const char *index_path,
                         const char *index_a_path, bsdb_mph **out);
 
+/* ---------------------------------------------------------------------------
+ * F4: the check of a finished database, batched on the device -- what
+ * Builder -v does one synchronous lookup at a time (Builder.java:184-228:
+ * getLong, the index.db slot, the kv.db record, a key compare).  Every record
+ * goes key -> signature -> rank (checked getLong, GOV:557-569) -> slot in ONE
+ * fused pass; a record passes when its key is accepted and the slot at its
+ * rank holds the record's own big-endian address (and, index.approximate, the
+ * first min(vlen, 8) bytes of its own value; the bytes past vlen are not
+ * compared, W:141).  Record addresses are distinct by construction (partition
+ * and file offset), so n passing records over an index.db of n slots occupy n
+ * different ranks: the address test is the bijection test.
+ *
+ * The report is uint64_t out[BSDB_VERIFY_WORDS]:
+ *   [0] records seen      [1] rejected (getLong gave -1)
+ *   [2] in_window (accepted records whose rank lay in a window; every window
+ *       together covers [0, n), so a clean run has [2] = [0] - [1])
+ *   [3] wrong_addr        [4] wrong_value (counted independently of [3])
+ *   [5] min_bad_addr: the smallest address among rejected / wrong_addr /
+ *       wrong_value records (UINT64_MAX when none)
+ *   [6] structure flags: bit 0 = E is not a valid offset array (E[0] = 0, low
+ *       56 bits non-decreasing, E[m] = n; only a valid E keeps every lookup
+ *       inside values[]: an imported hash.db is untrusted), bit 1 = index.db is
+ *       not 8n bytes (or index_a.db, index.approximate), bit 2 = [0] != n
+ *   [7] windows used
+ * bsdb_dev_verify_*: records resident on the device (keys as in
+ * bsdb_dev_hash_*: `count` of them, fixed-length keys at a 4-byte aligned
+ * address; the address of record i is d_addr[i], or
+ * addr_base + addr_stride * (first + i) when d_addr is NULL; d_value8 / d_vlen
+ * as in bsdb_dev_index_scatter, read only with d_index_a) against the MPHF
+ * arrays of bsdb_dev_lookup and the slots of the ranks [start, start + len) in
+ * d_index (and d_index_a, 8-byte aligned, NULL in exact mode).  Asynchronous.
+ * They ACCUMULATE into d_out[0..5] (the caller zeroes d_out and sets [5] to
+ * all ones; several calls, e.g. one per key shard, add up) and set bit 0 of
+ * d_out[6] when E is invalid, in which case no record is looked up.
+ * bsdb_mph_verify_index_*: records in host memory as for bsdb_index_put_*,
+ * the index files read from disk a window of ranks at a time (windows = 0: the
+ * fewest windows whose slots fit half of the free HBM); with several windows
+ * every window's pass sees all records: [0] and [1] come from the first pass,
+ * [2..4] are summed, [5] is the minimum.  bsdb_kv_verify_index: the records
+ * from the kv.db scan of bsdb_kv_build_index, each parsed chunk verified as it
+ * arrives (host memory bounded as there; one rescan per window).
+ * Returns: BSDB_EINVAL for bad arguments (before any device call),
+ * BSDB_EFILE for a file that cannot be read, BSDB_EVERIFY with `out` filled
+ * when any of [1], [3], [4], [6] is non-zero or [2] != [0] - [1], else BSDB_OK.
+ * Flag bits 0 and 1 end the call before any record pass ([0] = 0).
+ * ------------------------------------------------------------------------- */
+#define BSDB_VERIFY_WORDS 8
+int bsdb_dev_verify_fixed(bsdb_ctx *ctx, const uint8_t *d_keys, uint32_t key_len, uint64_t count,
+                          const uint64_t *d_addr, uint64_t addr_base, uint64_t addr_stride, uint64_t first,
+                          const uint64_t *d_value8, const uint8_t *d_vlen, uint64_t n, uint64_t num_buckets,
+                          const uint64_t *d_E, const uint64_t *d_values, uint32_t width, const uint64_t *d_sigbits,
+                          uint64_t start, uint64_t len, const uint64_t *d_index, const uint8_t *d_index_a,
+                          uint64_t *d_out, void *stream);
+int bsdb_dev_verify_var(bsdb_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offsets,
+                        uint64_t count, const uint64_t *d_addr, uint64_t addr_base, uint64_t addr_stride,
+                        uint64_t first, const uint64_t *d_value8, const uint8_t *d_vlen, uint64_t n,
+                        uint64_t num_buckets, const uint64_t *d_E, const uint64_t *d_values, uint32_t width,
+                        const uint64_t *d_sigbits, uint64_t start, uint64_t len, const uint64_t *d_index,
+                        const uint8_t *d_index_a, uint64_t *d_out, void *stream);
+int bsdb_mph_verify_index_fixed(bsdb_mph *mph, const uint8_t *h_keys, uint32_t key_len, uint64_t count,
+                                const uint64_t *h_addr, const uint64_t *h_value8, const uint8_t *h_vlen,
+                                int approximate, const char *index_path, const char *index_a_path, uint32_t windows,
+                                uint64_t *out);
+int bsdb_mph_verify_index_var(bsdb_mph *mph, const uint8_t *h_blob, const uint64_t *h_off, uint64_t count,
+                              const uint64_t *h_addr, const uint64_t *h_value8, const uint8_t *h_vlen,
+                              int approximate, const char *index_path, const char *index_a_path, uint32_t windows,
+                              uint64_t *out);
+int bsdb_kv_verify_index(bsdb_mph *mph, const char *kv_base, int partitions, int format, uint32_t block_size,
+                         int threads, int approximate, const char *index_path, const char *index_a_path,
+                         uint32_t windows, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

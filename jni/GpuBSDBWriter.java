@@ -63,6 +63,10 @@ public class GpuBSDBWriter {
     private static final int DEVICE = Integer.getInteger("bsdb.gpu.device", 0);
     /** Keys (and key bytes) one put() thread collects before they go to the device. */
     private static final int BATCH_KEYS = 1 << 18, BATCH_BYTES = 16 << 20;
+    /** Keeps the MPHF on the device past buildIndex for verify() (-Dbsdb.build.verify, default off). */
+    private static final boolean KEEP_FOR_VERIFY = Boolean.getBoolean("bsdb.build.verify");
+    /** Words of the verification report (BSDB_VERIFY_WORDS). */
+    private static final int VERIFY_WORDS = 8;
 
     private final File basePath;
     private final KVWriter kvWriter;
@@ -80,6 +84,7 @@ public class GpuBSDBWriter {
     private final ThreadLocal<Batch> keyBatch;
     private long gpuMph;
     private boolean indexWritten;
+    private boolean released;
 
     public GpuBSDBWriter(File basePath, File tmpDir, int checksumBits, long passCacheSize, boolean compact,
                          boolean compress, int compressBlockSize, int sharedDictSize, boolean approximateMode)
@@ -185,9 +190,42 @@ public class GpuBSDBWriter {
         try {
             if (!indexWritten) passLoop();
         } finally {
-            GpuBuild.mphFree(gpuMph);
-            GpuBuild.close(ctx);
+            if (!KEEP_FOR_VERIFY) release();
         }
+    }
+
+    /**
+     * Builder -v (Builder.java:184-228) on the device: every record of the finished kv.db files goes
+     * key -> rank -> index.db slot (-> index_a.db value bytes) in one fused pass (bsdb_kv_verify_index),
+     * instead of one SyncReader.getAsBytes per record.  Needs the MPHF still on the device: run the JVM
+     * with -Dbsdb.build.verify=true, which keeps it past buildIndex; verify() releases it.  Returns the
+     * report (bsdb_mi355x.h, BSDB_VERIFY_WORDS); a database that is not clean throws.
+     */
+    public long[] verify() throws IOException {
+        if (released) throw new IllegalStateException("the MPHF was released: run with -Dbsdb.build.verify=true");
+        if (nativeFormat < 0) throw new IOException("verify reads the compact and blocked kv.db layouts only");
+        final long[] report = new long[VERIFY_WORDS];
+        try {
+            final PartitionedKVWriter pw = (PartitionedKVWriter) kvWriter;
+            final int blockSize = nativeFormat == 1 ? ((BlockedKVWriter) kvWriter).blockSize : 0;
+            final boolean clean = GpuBuild.kvVerifyIndex(gpuMph, new File(basePath, FILE_NAME_KV_DATA).getPath(),
+                    pw.partitions, nativeFormat, blockSize, 0, approximateMode, indexFile().getPath(),
+                    approximateIndexFile().getPath(), 0, report);
+            if (!clean)
+                throw new IOException("verification failed: " + report[1] + " rejected, " + report[3]
+                        + " wrong addresses, " + report[4] + " wrong values, flags " + report[6] + " over "
+                        + report[0] + " records");
+        } finally {
+            release();
+        }
+        return report;
+    }
+
+    private void release() {
+        if (released) return;
+        released = true;
+        GpuBuild.mphFree(gpuMph);
+        GpuBuild.close(ctx);
     }
 
     // W:112-155: passSize = min(n, ps/8) slots a pass, one kvWriter.forEach per

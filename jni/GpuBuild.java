@@ -95,4 +95,10 @@ public final class GpuBuild {
     public static native long kvBuildIndex(long ctx, String kvBase, int partitions, int format, int blockSize,
                                            int threads, int checksumBits, boolean approximate, String indexPath,
                                            String indexAPath);
+    // F4: Builder -v on the device: the finished files checked record by record in one fused pass
+    // (key -> rank -> index.db slot -> index_a.db bytes); report[0..7] = records, rejected, inWindow,
+    // wrongAddr, wrongValue, minBadAddr, flags, windows; true when the database is clean
+    public static native boolean kvVerifyIndex(long mph, String kvBase, int partitions, int format, int blockSize,
+                                               int threads, boolean approximate, String indexPath, String indexAPath,
+                                               int windows, long[] report);
 }

@@ -280,3 +280,17 @@ JNIEXPORT jlong JF(kvBuildIndex)(JNIEnv *env, jclass c, jlong ctx, jstring kv, j
     if (rc) { fail(env, rc); return 0; }
     return (jlong)(intptr_t)m;
 }
+/* F4: the database check; BSDB_EVERIFY is an answer (false, report filled), every other code throws */
+JNIEXPORT jboolean JF(kvVerifyIndex)(JNIEnv *env, jclass c, jlong mph, jstring kv, jint parts, jint fmt, jint bs,
+                                     jint threads, jboolean approx, jstring ip, jstring ap, jint windows,
+                                     jlongArray report) {
+    if (!report || (*env)->GetArrayLength(env, report) < BSDB_VERIFY_WORDS) { fail(env, BSDB_EINVAL); return 0; }
+    const char *k = utf(env, kv), *i = utf(env, ip), *a = utf(env, ap);
+    uint64_t out[BSDB_VERIFY_WORDS] = {0};
+    int rc = bsdb_kv_verify_index(P(mph), k, parts, fmt, (uint32_t)bs, threads, approx, i, a, (uint32_t)windows, out);
+    unutf(env, kv, k); unutf(env, ip, i); unutf(env, ap, a);
+    if (rc == BSDB_EVERIFY) rc = 1;  /* not an error: the report says what is wrong */
+    else CHECK(rc);
+    if (rc >= 0) (*env)->SetLongArrayRegion(env, report, 0, BSDB_VERIFY_WORDS, (const jlong *)out);
+    return (jboolean)(rc == BSDB_OK);
+}
