@@ -61,7 +61,7 @@ struct bsdb_ctx {
     int d13_variant = 13;  // 13-byte keys' pass-1 kernel (BSDB_D13_VARIANT, see pass1_select): the same results under each
     int d13_copies = 8;     // region copies of the binned 13-byte kernel (BSDB_D13_COPIES=8|16|32)
     uint64_t chunk_keys = 0;  // keys per pass-1 launch (0 = default)
-    uint64_t span_max = 0;    // pass-1 launches per pass 2, at most (0 = default; BSDB_SPAN_MAX)
+    uint64_t span_max = 0;    // pass-1 launches per pass 2, at most (0 = no limit; BSDB_SPAN_MAX)
     int fused = -1;  // 13-byte keys, single-pass kernel: -1 = what mode 0 picks (BSDB_FUSED), 0 off, 1 on
     int pipe = -1;   // pass 2 of a chunk beside pass 1 of the next: -1 default, 0 off, 1 on (BSDB_PIPE)
     uint64_t pipe_chunks = 0;  // chunks of the pipelined histogram (0 = default; BSDB_PIPE_CHUNKS)
@@ -166,13 +166,11 @@ static void comm_destroy(bsdb_ctx *c);  // capi_comm.hip
 
 namespace {
 
-// Keys per pass-1 LAUNCH (bsdb_set_chunk_keys).  Measured: 2^32 286 G keys/s,
-// 2^33 284, one launch (13.2e9) 266.  Pass 2 runs once per SPAN of up to
-// MAX_SPAN_LAUNCHES launches (histogram_impl), not once per launch.
+// Keys per pass-1 LAUNCH (bsdb_set_chunk_keys).  A span's launches append to one region set and pass 2 runs once
+// per span (histogram_impl), so the length costs pass 2 and the workspace nothing.  C4 step ms, median of 3
+// (profiles/launch_length/): 2^32 42.73, 2^31 42.67, 2^30 42.72, 2^29 42.96, 2^28 43.37, 2^27 44.32 -- level down to
+// 2^30, then ~18 us per further launch.  Longer (earlier kernel): 2^33 284 G keys/s against 286, one launch 266.
 constexpr uint64_t DEFAULT_CHUNK_KEYS = 1ULL << 32;
-// k_pass2_plan (one workgroup) scans P * (J * nmain + ntail) items: 19 368 at
-// C4's 269 bins, 8 copies and J = 8
-constexpr uint64_t MAX_SPAN_LAUNCHES = 8;
 
 // BSDB_DEBUG=1: every failing HIP call behind an EIO is reported on stderr
 // with its source line (the return code alone does not say which call failed)
@@ -586,12 +584,23 @@ Pass1Sel pass1_select(const bsdb_ctx *c, bool var, uint32_t key_len, bool seed0,
     return binned_layout(sel, VARE_MAXP, VARE_BIN_IDS, m) ? sel : none;
 }
 
-// Region capacities: a bin's expected share per region copy plus 8 sigma and
-// two tiles of slack (and, for padded runs, 7 pads per tile); a fill beyond
-// cap raises the overflow flag and the chunk is recounted with direct
-// atomics.  Layout of the id buffer: [nmain][P][cap], then the tail kernel's
-// [ntail][P][cap_tail].
-PartPlan plan_partitions(const bsdb_ctx *c, uint64_t chunk, uint64_t m, const Pass1Sel &sel) {
+// Region capacities of a span: `span` keys in launches of `launch` keys, all
+// appending to one region set.  Every launch deals its tiles round-robin over
+// the copies from copy 0 on, so a copy takes at most ceil(tiles / copies)
+// tiles of each launch (launches of 8k + 1 tiles all give the odd tile to
+// copy 0).  cap = a bin's expected share of the keys of those tiles plus 2 %,
+// 8 sigma and two tiles of slack, plus the pads of padded runs:
+//  * k_pass1_d13e pads once per workgroup per bin per launch (at most 7 ids,
+//    in the copy of the workgroup's last tile; the last tiles of a launch's G
+//    workgroups are G consecutive tiles, so at most ceil(G / copies) of them
+//    end in one copy): 7 * (G / copies + 1) * launches;
+//  * k_pass1_vare pads every tile's run: 7 per tile of the copy.
+// A fill beyond cap raises the overflow flag and the span is recounted with
+// direct atomics.  *keys_per_copy: the most keys one copy takes (a bin's
+// cursor cannot pass it).  Layout of the id buffer: [nmain][P][cap], then the
+// tail kernel's [ntail][P][cap_tail].
+PartPlan plan_partitions(const bsdb_ctx *c, uint64_t span, uint64_t launch, uint64_t m, const Pass1Sel &sel,
+                         uint64_t *keys_per_copy = nullptr) {
     PartPlan p{};
     const bool d13 = sel.k != nullptr, binned = sel.binned;
     p.bin_shift = sel.bin_shift;
@@ -599,27 +608,36 @@ PartPlan plan_partitions(const bsdb_ctx *c, uint64_t chunk, uint64_t m, const Pa
     p.capb = sel.capb;
     const double frac = std::min(1.0, (double)(1ULL << p.bin_shift) / (double)m);
     p.nmain = binned ? (uint32_t)c->d13_copies : NCOPY;
-    const double e = (double)chunk * frac / p.nmain;
-    p.cap = round64(e * 1.02 + 8.0 * std::sqrt(e) + 2 * P1_TILE + 64);
+    launch = std::min(launch, span);
+    const uint64_t tile = d13 ? sel.tile : (uint64_t)P1_TILE;
+    const uint64_t full = span / launch, rest = span % launch;  // whole launches, keys of a shorter last one
+    const uint64_t launches = full + (rest ? 1 : 0);
+    auto copy_tiles = [&](uint64_t keys) { return ((keys + tile - 1) / tile + p.nmain - 1) / p.nmain; };
+    const uint64_t tiles_per_copy = full * copy_tiles(launch) + copy_tiles(rest);
+    const uint64_t kpc = std::min(span, tiles_per_copy * tile);
+    if (keys_per_copy) *keys_per_copy = kpc;
+    const double e = (double)kpc * frac;
+    double pads = 0;
     p.ntail = 0;
     p.cap_tail = 0;
     if (d13) {
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sel.k, sel.nt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
         per_cu = std::min(per_cu, 2048 / sel.nt);  // at most 32 waves per CU
-        const uint64_t tiles = (chunk + sel.tile - 1) / sel.tile;
+        const uint64_t tiles = (launch + sel.tile - 1) / sel.tile;
         p.grid_d13 = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->num_cus * per_cu);
         // measurement aid: fewer persistent workgroups (BSDB_D13_GRID, e.g. CUs left for other work)
         if (const char *v = getenv("BSDB_D13_GRID")) p.grid_d13 = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(p.grid_d13, atoll(v)));
-        if (binned) {
-            const double tiles_per_copy = (double)tiles / p.nmain + 1;
-            p.cap = round64(e * 1.02 + 8.0 * std::sqrt(e) + 7.0 * tiles_per_copy + 2 * P1_TILE + 64);
-        }
+        if (binned && sel.windowed)
+            pads = 7.0 * (p.grid_d13 / p.nmain + 1) * (double)launches;
+        else if (binned)
+            pads = 7.0 * (double)tiles_per_copy;
         // the tail (< 2 tiles of the persistent kernel) goes to k_pass1 in
         // blocks of P1_TILE keys, one region each
         p.ntail = NCOPY;
         p.cap_tail = round64(std::max<uint64_t>(P1_TILE, sel.tile) + 64);
     }
+    p.cap = round64(e * 1.02 + 8.0 * std::sqrt(e) + pads + 2 * P1_TILE + 64);
     return p;
 }
 
@@ -746,38 +764,47 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
         return d13 && !pipe_pl && ch < n && ch >= sel.tile ? ch / sel.tile * sel.tile : ch;
     };
     chunk = whole_tiles(chunk);
-    PartPlan pp = plan_partitions(c, chunk, m, sel);
-    // the id buffers take at most half of the device memory left (workspace
-    // included); the 13-byte kernel addresses one region set (P segments)
-    // with 32-bit offsets
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    const size_t budget = (free_b + c->ids_bytes) / 2 / (pipe_pl ? 2 : 1);
-    while (chunk > 2 * P1_TILE && (pp.ids_elems() * sizeof(uint16_t) > budget ||
-                                   (uint64_t)pp.nparts * pp.cap >= (1ULL << 32))) {
-        chunk = whole_tiles(std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE));
-        pp = plan_partitions(c, chunk, m, sel);
-    }
-    // A span: J consecutive pass-1 launches of chunk keys, each into a region
-    // set of its own, then ONE pass 2 over all of them (its workgroups flush
-    // their LDS tables once per span, not once per launch).  Layout of a
-    // span's ids: [J][nmain][P][cap], then the tail regions; of its cursors:
-    // [J][nmain][P], then the tail's -- to pass 2 one launch with J * nmain
-    // main regions.  As many launches as the memory budget above holds, at
-    // most MAX_SPAN_LAUNCHES (k_pass2_plan's item count), c->span_max if set.
+    // A span: J consecutive pass-1 launches of chunk keys, all appending to
+    // ONE region set (the kernels reserve their runs with a cursor atomic per
+    // (copy, bin) and never assume a cursor starts at 0), then ONE pass 2
+    // (its workgroups flush their LDS tables once per span, not once per
+    // launch).  Layout of a span's ids: [nmain][P][cap], then the tail
+    // regions; of its cursors: [nmain][P], then the tail's; cap is sized for
+    // the span's keys, so pass 2 and the workspace see the same layout
+    // whatever the launch length.  The whole call is one span unless
+    // c->span_max (launches per span at most) or the rules below shorten it.
     // A persistent kernel's launches must be whole tiles of it: every launch
     // but the span's last then runs entirely in that kernel, and the span
     // has one set of tail regions.  (The one-tile-per-workgroup kernels have
     // no tail: any launch length, a multiple of P1_TILE.)
-    const size_t set_elems = (size_t)pp.nparts * pp.nmain * pp.cap;               // ids of one launch's main regions
-    const size_t tail_elems = (size_t)pp.nparts * pp.ntail * pp.cap_tail;         // ids of the tail regions
     uint64_t J = 1;
     if (!pipe_pl && n > chunk && (!d13 || chunk % sel.tile == 0)) {
-        const uint64_t jmax = c->span_max ? c->span_max : MAX_SPAN_LAUNCHES;
-        J = std::min<uint64_t>({(n + chunk - 1) / chunk, jmax, MAX_SPAN_LAUNCHES});
-        while (J > 1 && (J * set_elems + tail_elems) * sizeof(uint16_t) > budget) --J;
+        J = (n + chunk - 1) / chunk;
+        if (c->span_max) J = std::min<uint64_t>(J, c->span_max);
     }
-    const uint32_t R = (uint32_t)J * pp.nmain + pp.ntail;
+    // The id buffers take at most half of the device memory left (workspace
+    // included); the kernels address one region copy (P segments of cap ids)
+    // with 32-bit offsets and count a segment's fill in 32 bits.  These bound
+    // the SPAN: it is halved until they hold, and only a span of one launch
+    // halves the launch.
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const size_t budget = (free_b + c->ids_bytes) / 2 / (pipe_pl ? 2 : 1);
+    uint64_t kpc = 0;  // keys one copy takes at most: the bound of a bin's cursor
+    PartPlan pp = plan_partitions(c, std::min(n, J * chunk), chunk, m, sel, &kpc);
+    while (pp.ids_elems() * sizeof(uint16_t) > budget || (uint64_t)pp.nparts * pp.cap >= (1ULL << 32) ||
+           kpc >= (1ULL << 32)) {
+        if (J > 1)
+            J = (J + 1) / 2;
+        else if (chunk > 2 * P1_TILE)
+            chunk = whole_tiles(std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE));
+        else
+            break;
+        pp = plan_partitions(c, std::min(n, J * chunk), chunk, m, sel, &kpc);
+    }
+    const size_t set_elems = (size_t)pp.nparts * pp.nmain * pp.cap;               // ids of the span's main regions
+    const size_t tail_elems = (size_t)pp.nparts * pp.ntail * pp.cap_tail;         // ids of the tail regions
+    const uint32_t R = pp.nmain + pp.ntail;
     // Pass 2 of chunk i overlapped with pass 1 of chunk i + 1 (13-byte
     // windowed keys, several chunks): two id buffers; pass 1 on the caller's
     // stream over all CUs but the ones pass 2 keeps (its workgroups hold 128
@@ -786,7 +813,7 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     // pass 1 and the last pass 2 get the whole chip.
     const bool pipe = pipe_pl && n > chunk;
     const int nbuf = pipe ? 2 : 1;
-    const size_t ids_per_buf = J * set_elems + tail_elems, cur_per_buf = (size_t)pp.nparts * R;
+    const size_t ids_per_buf = set_elems + tail_elems, cur_per_buf = (size_t)pp.nparts * R;
     int rc = grow(&c->ids, &c->ids_bytes, nbuf * ids_per_buf * sizeof(uint16_t));
     if (rc) return rc;
     rc = grow((void **)&c->cursor, &c->cursor_bytes,
@@ -833,15 +860,13 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
         as.cursor = c->cursor + b * cur_per_buf;
         as.overflow = c->overflow + 4 * b;
         uint64_t *pref = c->p2_pref + b * (cur_per_buf + 1);
-        // the tail regions follow the main regions of the jn launches
-        uint16_t *const tail_ids = as.ids + jn * set_elems;
-        uint32_t *const tail_cur = as.cursor + jn * pp.nmain * pp.nparts;
+        // the tail regions follow the span's main regions
+        uint16_t *const tail_ids = as.ids + set_elems;
+        uint32_t *const tail_cur = as.cursor + pp.nmain * pp.nparts;
         P2Layout L = L0;
         L.ids = as.ids;
         L.cursor = as.cursor;
         L.overflow = as.overflow;
-        L.nmain = (uint32_t)jn * pp.nmain;
-        const size_t cur_span = (size_t)pp.nparts * (L.nmain + L.ntail);
         as.n = ns;
         if (var) {
             as.offsets = offsets + s0;
@@ -850,15 +875,13 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
             as.blob_bytes = pipe ? blob_bytes - s0 * key_len : ns * key_len;
         }
         if (pipe && i >= 2) HIP_OK(hipStreamWaitEvent(s, c->pipe_ev[2 + b], 0));  // pass 2 of chunk i - 2 read buffer b
-        HIP_OK(hipMemsetAsync(as.cursor, 0, sizeof(uint32_t) * cur_span, s));
+        HIP_OK(hipMemsetAsync(as.cursor, 0, sizeof(uint32_t) * cur_per_buf, s));
         HIP_OK(hipMemsetAsync(as.overflow, 0, sizeof(uint32_t), s));
         for (uint64_t j = 0; j < jn; ++j, ++i) {
             const uint64_t k0 = s0 + j * chunk, nk = std::min(chunk, n - k0);
             const bool first = k0 == 0, last_of_span = j + 1 == jn;
-            // launch j's region set
+            // launch j appends to the span's regions (as.ids, as.cursor)
             P1Args ac = as;
-            ac.ids = as.ids + j * set_elems;
-            ac.cursor = as.cursor + j * pp.nmain * pp.nparts;
             ac.n = nk;
             if (var) {
                 ac.offsets = offsets + k0;

@@ -242,8 +242,12 @@ int bsdb_set_frontend(bsdb_ctx *ctx, int frontend);
  * 0 = serial chunks, 1 = pipelined; chunks / p2_cus 0 = defaults (8 chunks,
  * CUs / 8).  Results are identical either way. */
 int bsdb_set_pipeline(bsdb_ctx *ctx, int mode, uint64_t chunks, uint32_t p2_cus);
-/* Keys per pass-1 launch (chunk) of the partitioned path (0 = default).  Pass
- * 2 runs once per span of several such launches. */
+/* Keys per pass-1 launch (chunk) of the partitioned path (0 = default);
+ * rounded down to whole tiles of the pass-1 kernel.  The launches of a span
+ * (the whole call, memory permitting) append to one set of id regions sized
+ * for the span, and pass 2 runs once per span: the launch length changes
+ * neither the workspace nor what pass 2 reads, only how pass 1 is cut into
+ * launches.  Results are identical for every value. */
 int bsdb_set_chunk_keys(bsdb_ctx *ctx, uint64_t chunk_keys);
 /* Chunks the partitioned path recounted with direct atomics since open
  * because a partition region or LDS bin overflowed (adversarial key sets,

@@ -24,7 +24,10 @@ def main():
               "pass2_ms": lambda r: r["kernel_ms_per_step"]["pass2"]}
     out = {}
     # profiles/pass1_requests/: req_a, req_b, req_c; profiles/pass2_span/: span_a, span_ab, span_c, final
-    for name in ("parent", "req_a", "req_b", "req_c", "span_a", "span_ab", "span_c", "all", "final"):
+    # profiles/launch_length/: final (the default launch length), chunk_2p<k> (bench.py --chunk 2^k)
+    names = ["parent", "req_a", "req_b", "req_c", "span_a", "span_ab", "span_c", "all", "final"]
+    names += sorted(f[:-6] for f in os.listdir(d) if f.startswith("chunk_2p") and f.endswith(".jsonl"))
+    for name in names:
         path = os.path.join(d, name + ".jsonl")
         if not os.path.exists(path):
             continue
