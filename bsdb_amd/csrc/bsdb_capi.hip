@@ -39,6 +39,7 @@
 #include "mph_kernels.hip"
 #include "gov_kernels.hip"
 #include "verify_kernels.hip"
+#include "hist_plan.hpp"
 
 using namespace bsdb;
 
@@ -165,12 +166,6 @@ struct ProfScope {
 static void comm_destroy(bsdb_ctx *c);  // capi_comm.hip
 
 namespace {
-
-// Keys per pass-1 LAUNCH (bsdb_set_chunk_keys).  A span's launches append to one region set and pass 2 runs once
-// per span (histogram_impl), so the length costs pass 2 and the workspace nothing.  C4 step ms, median of 3
-// (profiles/launch_length/): 2^32 42.73, 2^31 42.67, 2^30 42.72, 2^29 42.96, 2^28 43.37, 2^27 44.32 -- level down to
-// 2^30, then ~18 us per further launch.  Longer (earlier kernel): 2^33 284 G keys/s against 286, one launch 266.
-constexpr uint64_t DEFAULT_CHUNK_KEYS = 1ULL << 32;
 
 // BSDB_DEBUG=1: every failing HIP call behind an EIO is reported on stderr
 // with its source line (the return code alone does not say which call failed)
@@ -455,535 +450,8 @@ int usable_cpus() {
     return n;
 }
 
-// ---- pass-1 dispatch over (source layout, epilogue) ------------------------
-// One-tile-per-workgroup launches: tiles * 512 work-items must stay below 2^32
-// (a dispatch packet's grid size is 32-bit), so callers split larger key sets.
-constexpr uint64_t MAX_TILES_PER_LAUNCH = (1ULL << 32) / P1_THREADS - 1;
-
-template <int EPI>
-void launch_pass1(const P1Args &a0, bool var, uint32_t key_len, uint64_t tiles, hipStream_t s, int frontend) {
-    if (tiles > MAX_TILES_PER_LAUNCH) {
-        // split into launches of whole tiles (keys, offsets and outputs shifted)
-        for (uint64_t t0 = 0; t0 < tiles; t0 += MAX_TILES_PER_LAUNCH) {
-            const uint64_t nt = std::min(MAX_TILES_PER_LAUNCH, tiles - t0);
-            P1Args a = a0;
-            const uint64_t k0 = t0 * P1_TILE;
-            a.n = std::min<uint64_t>(a0.n - k0, nt * P1_TILE);
-            if (var) {
-                a.offsets = a0.offsets + k0;
-            } else {
-                a.keys = a0.keys + k0 * key_len;
-                a.blob_bytes = a0.blob_bytes - k0 * key_len;
-            }
-            if (a.sig) a.sig = a0.sig + 2 * k0;
-            launch_pass1<EPI>(a, var, key_len, nt, s, frontend);
-        }
-        return;
-    }
-    const P1Args &a = a0;
-    const dim3 g((uint32_t)tiles), b(P1_THREADS);
-    if (var && frontend == 2) {
-        k_pass1<SRC_VAR, EPI, 1, 0><<<g, b, 0, s>>>(a);
-    } else if (var) {
-        k_pass1<SRC_VARSTAGED, EPI, 1, 0><<<g, b, 0, s>>>(a);
-    } else if (key_len == 13 && frontend != 1) {
-        k_pass1<SRC_DIRECT13, EPI, 4, 13><<<g, b, 0, s>>>(a);
-    } else if (key_len == 13) {
-        k_pass1<SRC_STAGED13, EPI, 4, 13><<<g, b, 0, s>>>(a);
-    } else if (key_len >= 1 && key_len <= 13) {
-        k_pass1<SRC_STAGED, EPI, 4, 0><<<g, b, 0, s>>>(a);
-    } else if (key_len >= 14 && key_len <= 26) {
-        k_pass1<SRC_STAGED, EPI, 2, 0><<<g, b, 0, s>>>(a);
-    } else if (key_len >= 27 && key_len <= 52) {
-        k_pass1<SRC_STAGED, EPI, 1, 0><<<g, b, 0, s>>>(a);
-    } else {
-        k_pass1<SRC_FIXED_DIRECT, EPI, 1, 0><<<g, b, 0, s>>>(a);
-    }
-}
-
-struct PartPlan {
-    uint32_t nparts;     // region bins: bucket >> bin_shift
-    uint32_t bin_shift;  // <= PART_SHIFT; bins nest in the 32768-bucket pass-2 partitions
-    uint32_t capb;       // k_pass1_d13e: ids per LDS bin
-    uint32_t nmain;      // region copies shared by the workgroups of one XCD
-    uint32_t ntail;      // 13-byte path: NCOPY regions of the bounds-checked tail kernel
-    uint32_t grid_d13;   // persistent workgroups of the 13-byte kernel (0 = generic path)
-    uint64_t cap;        // ids per (bin, main region), multiple of 64
-    uint64_t cap_tail;   // ids per (bin, tail region), multiple of 64
-    size_t ids_elems() const { return (size_t)nparts * (nmain * cap + ntail * cap_tail); }
-};
-
-uint64_t round64(double x) { return ((uint64_t)x + 63) & ~63ULL; }
-
-using D13Kernel = void (*)(P1Args, uint64_t);
-
-// The persistent pass-1 kernel of a key set and its bin layout, or none: the
-// one-tile-per-workgroup kernels of launch_pass1.
-struct Pass1Sel {
-    D13Kernel k;         // nullptr: none
-    int nt;              // workgroup size
-    uint64_t tile;       // keys per tile
-    bool binned;         // runs padded to 8 ids, region copies = d13_copies
-    bool windowed;       // fixed-length keys read as 16-byte windows (k_pass1_d13e, k_pass1_d13), not k_pass1_vare
-    uint32_t bin_shift;  // region bins: bucket >> bin_shift
-    uint32_t nparts;
-    uint32_t capb;       // binned: ids per LDS bin
-};
-
-// Bins of a binned kernel: the smallest bin_shift with ceil(m >> shift) <=
-// maxp, so a tile fills each LDS bin to tile/P on average while a bin holds
-// bin_ids/P >= 2.25x that (>= 8 sigma).
-bool binned_layout(Pass1Sel &sel, uint32_t maxp, uint32_t bin_ids, uint64_t m) {
-    uint32_t shift = 0;
-    while (shift <= (uint32_t)PART_SHIFT && ((m + (1ULL << shift) - 1) >> shift) > (uint64_t)maxp) ++shift;
-    if (shift > (uint32_t)PART_SHIFT) return false;
-    sel.bin_shift = shift;
-    sel.nparts = (uint32_t)((m + (1ULL << shift) - 1) >> shift);
-    sel.capb = std::min<uint32_t>((bin_ids / sel.nparts) & ~7u, (uint32_t)sel.tile + 8);
-    return true;
-}
-
-// The one place that chooses pass 1's kernel (two-pass path, m buckets):
-//  * 13-byte keys: k_pass1_d13e with its cursor atomic as a buffer atomic
-//    (VARIANT 13, the default; BSDB_D13_VARIANT=0: as a flat atomic); above
-//    its 288 bins (m > 288 * 32768), or with BSDB_D13_VARIANT=2, the round-1
-//    sort kernel k_pass1_d13 (up to 1024 partitions).  Every other value of
-//    the variable means 0.
-//  * 8 / 12 / 16-byte keys: k_pass1_d13e, a key's 16-byte window from its
-//    aligned start; BSDB_NO_FIXED_WINDOW=1 sends them to the var-len kernel
-//    instead (A/B switch for measurements).
-//  * variable-length keys and every other fixed length up to 32 B (as k * L
-//    offsets): k_pass1_vare.  (Fixed keys over 32 B: a 128-key group would
-//    overflow its LDS stage.)
-//  * none: a frontend other than 0, fixed keys of 0 or over 32 B, more bins
-//    than the kernel holds.
-// seed0: the kernels with the seed folded at compile time.
-Pass1Sel pass1_select(const bsdb_ctx *c, bool var, uint32_t key_len, bool seed0, uint64_t m) {
-    const uint32_t nparts = (uint32_t)((m + PART_BUCKETS - 1) / PART_BUCKETS);
-    const Pass1Sel none{nullptr, 0, 0, false, false, (uint32_t)PART_SHIFT, nparts, 0};
-    const Pass1Sel sort{k_pass1_d13<512>, 512, 512 * P1_KEYS_PER_THREAD, false, true, (uint32_t)PART_SHIFT, nparts, 0};
-    const bool sort_fits = nparts <= 1024;
-    if (c->frontend != 0) return none;
-    const bool k13 = !var && key_len == 13;
-    const bool window = k13 || (!var && (key_len == 8 || key_len == 12 || key_len == 16) && !getenv("BSDB_NO_FIXED_WINDOW"));
-    if (window) {
-        if (k13 && c->d13_variant == 2) return sort_fits ? sort : none;
-        D13Kernel k = key_len == 8    ? (seed0 ? k_pass1_d13e<0, true, 8> : k_pass1_d13e<0, false, 8>)
-                      : key_len == 12 ? (seed0 ? k_pass1_d13e<0, true, 12> : k_pass1_d13e<0, false, 12>)
-                      : key_len == 16 ? (seed0 ? k_pass1_d13e<0, true, 16> : k_pass1_d13e<0, false, 16>)
-                      : c->d13_variant == 13 ? (seed0 ? k_pass1_d13e<13, true> : k_pass1_d13e<13>)
-                                             : (seed0 ? k_pass1_d13e<0, true> : k_pass1_d13e<0>);
-        Pass1Sel sel{k, D13E_NT, D13E_TILE, true, true, 0, 0, 0};
-        if (binned_layout(sel, D13E_MAXP, D13E_BIN_IDS, m)) return sel;
-        return k13 && sort_fits ? sort : none;
-    }
-    if (!var && (key_len == 0 || key_len > 32)) return none;
-    D13Kernel k = var ? (seed0 ? k_pass1_vare<false, true> : k_pass1_vare<false>)
-                      : (seed0 ? k_pass1_vare<true, true> : k_pass1_vare<true>);
-    Pass1Sel sel{k, VARE_NT, VARE_TILE, true, false, 0, 0, 0};
-    return binned_layout(sel, VARE_MAXP, VARE_BIN_IDS, m) ? sel : none;
-}
-
-// Region capacities of a span: `span` keys in launches of `launch` keys, all
-// appending to one region set.  Every launch deals its tiles round-robin over
-// the copies from copy 0 on, so a copy takes at most ceil(tiles / copies)
-// tiles of each launch (launches of 8k + 1 tiles all give the odd tile to
-// copy 0).  cap = a bin's expected share of the keys of those tiles plus 2 %,
-// 8 sigma and two tiles of slack, plus the pads of padded runs:
-//  * k_pass1_d13e pads once per workgroup per bin per launch (at most 7 ids,
-//    in the copy of the workgroup's last tile; the last tiles of a launch's G
-//    workgroups are G consecutive tiles, so at most ceil(G / copies) of them
-//    end in one copy): 7 * (G / copies + 1) * launches;
-//  * k_pass1_vare pads every tile's run: 7 per tile of the copy.
-// A fill beyond cap raises the overflow flag and the span is recounted with
-// direct atomics.  *keys_per_copy: the most keys one copy takes (a bin's
-// cursor cannot pass it).  Layout of the id buffer: [nmain][P][cap], then the
-// tail kernel's [ntail][P][cap_tail].
-PartPlan plan_partitions(const bsdb_ctx *c, uint64_t span, uint64_t launch, uint64_t m, const Pass1Sel &sel,
-                         uint64_t *keys_per_copy = nullptr) {
-    PartPlan p{};
-    const bool d13 = sel.k != nullptr, binned = sel.binned;
-    p.bin_shift = sel.bin_shift;
-    p.nparts = sel.nparts;
-    p.capb = sel.capb;
-    const double frac = std::min(1.0, (double)(1ULL << p.bin_shift) / (double)m);
-    p.nmain = binned ? (uint32_t)c->d13_copies : NCOPY;
-    launch = std::min(launch, span);
-    const uint64_t tile = d13 ? sel.tile : (uint64_t)P1_TILE;
-    const uint64_t full = span / launch, rest = span % launch;  // whole launches, keys of a shorter last one
-    const uint64_t launches = full + (rest ? 1 : 0);
-    auto copy_tiles = [&](uint64_t keys) { return ((keys + tile - 1) / tile + p.nmain - 1) / p.nmain; };
-    const uint64_t tiles_per_copy = full * copy_tiles(launch) + copy_tiles(rest);
-    const uint64_t kpc = std::min(span, tiles_per_copy * tile);
-    if (keys_per_copy) *keys_per_copy = kpc;
-    const double e = (double)kpc * frac;
-    double pads = 0;
-    p.ntail = 0;
-    p.cap_tail = 0;
-    if (d13) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sel.k, sel.nt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        per_cu = std::min(per_cu, 2048 / sel.nt);  // at most 32 waves per CU
-        const uint64_t tiles = (launch + sel.tile - 1) / sel.tile;
-        p.grid_d13 = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->num_cus * per_cu);
-        // measurement aid: fewer persistent workgroups (BSDB_D13_GRID, e.g. CUs left for other work)
-        if (const char *v = getenv("BSDB_D13_GRID")) p.grid_d13 = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(p.grid_d13, atoll(v)));
-        if (binned && sel.windowed)
-            pads = 7.0 * (p.grid_d13 / p.nmain + 1) * (double)launches;
-        else if (binned)
-            pads = 7.0 * (double)tiles_per_copy;
-        // the tail (< 2 tiles of the persistent kernel) goes to k_pass1 in
-        // blocks of P1_TILE keys, one region each
-        p.ntail = NCOPY;
-        p.cap_tail = round64(std::max<uint64_t>(P1_TILE, sel.tile) + 64);
-    }
-    p.cap = round64(e * 1.02 + 8.0 * std::sqrt(e) + pads + 2 * P1_TILE + 64);
-    return p;
-}
-
-// The single-pass kernel (fused_kernels.hip) over the whole super-tiles of a
-// 13-byte key set: *done = the keys it covers (a multiple of 256 * 16384);
-// 0 when the set does not qualify.  Enqueue only.
-constexpr uint64_t FU_MIN_SUPER = 4;  // super-tiles per workgroup, at least
-
-int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t n, uint64_t seed, uint64_t m,
-                 uint32_t *counts, hipStream_t s, uint64_t *done) {
-    *done = 0;
-    const uint64_t per = (uint64_t)FU_OWNERS * FU_TILE;
-    if (c->num_cus != FU_OWNERS || m == 0 || m > (uint64_t)FU_OWNERS * (FU_TCAP - 2)) return BSDB_OK;
-    // a key's 16-byte window ends 3 bytes past it: whole super-tiles whose
-    // windows stay inside the blob
-    if (blob_bytes < 3) return BSDB_OK;
-    const uint64_t nsuper = std::min(n / per, (blob_bytes - 3) / 13 / per);
-    if (nsuper < FU_MIN_SUPER) return BSDB_OK;
-    // the owner tables count in u16: keep the mean bucket count far below 2^16
-    // (a wrap is detected and recounted, but costs the whole launch)
-    if (n / m > 16384) return BSDB_OK;
-    static int per_cu = -1;
-    if (per_cu < 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_hist13_fused<true>, FU_NT, 0) != hipSuccess)
-        per_cu = 0;
-    if (per_cu < 1) return BSDB_OK;  // every workgroup must be resident
-    const size_t sync_bytes = FU_SYNC_U64 * sizeof(uint64_t);
-    const size_t ring_bytes = (size_t)FU_SLOTS * FU_SLOT_BYTES;
-    int rc = grow(&c->fu_ring, &c->fu_ring_bytes, ring_bytes + sync_bytes);
-    if (rc) return rc;
-    FusedArgs fa{};
-    fa.keys = keys;
-    fa.nsuper = nsuper;
-    fa.seed = seed;
-    fa.mult = (uint32_t)(2 * m);
-    fa.m = (uint32_t)m;
-    fa.ring = (uint8_t *)c->fu_ring;
-    fa.sync = (uint64_t *)((uint8_t *)c->fu_ring + ring_bytes);
-    fa.overflow = c->overflow;
-    fa.counts = counts;
-    HIP_OK(hipMemsetAsync(fa.sync, 0, sync_bytes, s));
-    HIP_OK(hipMemsetAsync(c->overflow, 0, sizeof(uint32_t), s));
-    ++c->fu_launches;
-    {
-        ProfScope ps(c, s, 0, nsuper * per);
-        if (seed == 0 && !getenv("BSDB_NO_SEED0"))
-            k_hist13_fused<true><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-        else
-            k_hist13_fused<false><<<FU_OWNERS, FU_NT, 0, s>>>(fa);
-    }
-    // an overflow anywhere (adversarial sets): nothing was added; recount
-    P1Args af{};
-    af.keys = keys;
-    af.blob_bytes = blob_bytes;
-    af.key_len = 13;
-    af.n = nsuper * per;
-    af.seed = seed;
-    af.multiplier = 2 * m;
-    af.counts = counts;
-    af.overflow = c->overflow;
-    k_overflow_fallback<SRC_FIXED_DIRECT, 0><<<1024, P1_THREADS, 0, s>>>(af);
-    if ((rc = launch_status())) return rc;
-    *done = nsuper * per;
-    return BSDB_OK;
-}
-
-bool pipe_wanted(const bsdb_ctx *c) { return c->pipe == 1; }
-
-uint32_t pipe_p2_cus(const bsdb_ctx *c) {
-    const uint32_t k = c->pipe_cus ? c->pipe_cus : (uint32_t)c->num_cus / 8;  // 4 per XCD
-    return std::max<uint32_t>(1, std::min<uint32_t>(k, (uint32_t)c->num_cus / 2));
-}
-
-bool fused_wanted(const bsdb_ctx *c) {
-    if (c->hist_mode == 3) return true;
-    if (c->hist_mode != 0) return false;
-    if (c->fused >= 0) return c->fused == 1;
-    return false;
-}
-
-int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, uint64_t blob_bytes,
-                   uint32_t key_len, uint64_t n, uint64_t seed, uint64_t m, uint32_t *counts,
-                   hipStream_t s) {
-    if (n == 0) return BSDB_OK;
-    const bool var = offsets != nullptr;
-    if (!var && key_len == 13 && fused_wanted(c)) {
-        uint64_t done = 0;
-        const int rc = fused13_impl(c, keys, blob_bytes, n, seed, m, counts, s, &done);
-        if (rc) return rc;
-        if (done) return histogram_impl(c, keys + done * 13, nullptr, blob_bytes - done * 13, 13, n - done, seed, m,
-                                        counts, s);  // the rest (< one super-tile round): two-pass
-    }
-    P1Args a{};
-    a.keys = keys;
-    a.offsets = offsets;
-    a.blob_bytes = blob_bytes;
-    a.key_len = key_len;
-    a.seed = seed;
-    a.multiplier = 2 * m;
-    a.counts = counts;
-    const uint32_t nparts = (uint32_t)((m + PART_BUCKETS - 1) / PART_BUCKETS);
-    const bool atomic_mode = c->hist_mode == 2 || nparts > (uint32_t)MAX_PARTS;
-    // (mode 3 on a set the fused kernel does not take: the two-pass path)
-    if (atomic_mode) {
-        a.n = n;
-        ProfScope ps(c, s, 0, n);
-        launch_pass1<EPI_ATOMIC>(a, var, key_len, (n + P1_TILE - 1) / P1_TILE, s, c->frontend);
-        return launch_status();
-    }
-    uint64_t chunk = c->chunk_keys ? c->chunk_keys : DEFAULT_CHUNK_KEYS;
-    chunk = std::max<uint64_t>(P1_TILE, chunk / P1_TILE * P1_TILE);
-    chunk = std::min<uint64_t>(chunk, (n + P1_TILE - 1) / P1_TILE * P1_TILE);
-    // the persistent kernel, if any (BSDB_NO_SEED0: A/B switch for measurements)
-    const Pass1Sel sel = pass1_select(c, var, key_len, seed == 0 && !getenv("BSDB_NO_SEED0"), m);
-    const bool d13 = sel.k != nullptr;
-    const bool pipe_pl = pipe_wanted(c) && sel.windowed && sel.binned;
-    if (pipe_pl && !c->chunk_keys) {
-        // equal chunks of whole tiles: pass 2 of each beside pass 1 of the next
-        const uint64_t nch = c->pipe_chunks ? c->pipe_chunks : 8;
-        chunk = std::max<uint64_t>(sel.tile, ((n + nch - 1) / nch + sel.tile - 1) / sel.tile * sel.tile);
-    }
-    // several launches of a persistent kernel: whole tiles of it each, so
-    // that only a span's last launch leaves keys to the tail kernel
-    auto whole_tiles = [&](uint64_t ch) {
-        return d13 && !pipe_pl && ch < n && ch >= sel.tile ? ch / sel.tile * sel.tile : ch;
-    };
-    chunk = whole_tiles(chunk);
-    // A span: J consecutive pass-1 launches of chunk keys, all appending to
-    // ONE region set (the kernels reserve their runs with a cursor atomic per
-    // (copy, bin) and never assume a cursor starts at 0), then ONE pass 2
-    // (its workgroups flush their LDS tables once per span, not once per
-    // launch).  Layout of a span's ids: [nmain][P][cap], then the tail
-    // regions; of its cursors: [nmain][P], then the tail's; cap is sized for
-    // the span's keys, so pass 2 and the workspace see the same layout
-    // whatever the launch length.  The whole call is one span unless
-    // c->span_max (launches per span at most) or the rules below shorten it.
-    // A persistent kernel's launches must be whole tiles of it: every launch
-    // but the span's last then runs entirely in that kernel, and the span
-    // has one set of tail regions.  (The one-tile-per-workgroup kernels have
-    // no tail: any launch length, a multiple of P1_TILE.)
-    uint64_t J = 1;
-    if (!pipe_pl && n > chunk && (!d13 || chunk % sel.tile == 0)) {
-        J = (n + chunk - 1) / chunk;
-        if (c->span_max) J = std::min<uint64_t>(J, c->span_max);
-    }
-    // The id buffers take at most half of the device memory left (workspace
-    // included); the kernels address one region copy (P segments of cap ids)
-    // with 32-bit offsets and count a segment's fill in 32 bits.  These bound
-    // the SPAN: it is halved until they hold, and only a span of one launch
-    // halves the launch.
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    const size_t budget = (free_b + c->ids_bytes) / 2 / (pipe_pl ? 2 : 1);
-    uint64_t kpc = 0;  // keys one copy takes at most: the bound of a bin's cursor
-    PartPlan pp = plan_partitions(c, std::min(n, J * chunk), chunk, m, sel, &kpc);
-    while (pp.ids_elems() * sizeof(uint16_t) > budget || (uint64_t)pp.nparts * pp.cap >= (1ULL << 32) ||
-           kpc >= (1ULL << 32)) {
-        if (J > 1)
-            J = (J + 1) / 2;
-        else if (chunk > 2 * P1_TILE)
-            chunk = whole_tiles(std::max<uint64_t>(P1_TILE, chunk / 2 / P1_TILE * P1_TILE));
-        else
-            break;
-        pp = plan_partitions(c, std::min(n, J * chunk), chunk, m, sel, &kpc);
-    }
-    const size_t set_elems = (size_t)pp.nparts * pp.nmain * pp.cap;               // ids of the span's main regions
-    const size_t tail_elems = (size_t)pp.nparts * pp.ntail * pp.cap_tail;         // ids of the tail regions
-    const uint32_t R = pp.nmain + pp.ntail;
-    // Pass 2 of chunk i overlapped with pass 1 of chunk i + 1 (13-byte
-    // windowed keys, several chunks): two id buffers; pass 1 on the caller's
-    // stream over all CUs but the ones pass 2 keeps (its workgroups hold 128
-    // KiB of LDS, pass 1's 146 KiB: one per CU each, so the two launches
-    // split the chip); pass 2 on the context's second stream.  The first
-    // pass 1 and the last pass 2 get the whole chip.
-    const bool pipe = pipe_pl && n > chunk;
-    const int nbuf = pipe ? 2 : 1;
-    const size_t ids_per_buf = set_elems + tail_elems, cur_per_buf = (size_t)pp.nparts * R;
-    int rc = grow(&c->ids, &c->ids_bytes, nbuf * ids_per_buf * sizeof(uint16_t));
-    if (rc) return rc;
-    rc = grow((void **)&c->cursor, &c->cursor_bytes,
-              (nbuf * cur_per_buf + P1_SCRATCH_WG + (size_t)P1_SCRATCH_MAXWG * 1024) * sizeof(uint32_t));
-    if (rc) return rc;
-    rc = grow((void **)&c->p2_pref, &c->p2_pref_bytes, nbuf * (cur_per_buf + 1) * sizeof(uint64_t));
-    if (rc) return rc;
-    hipStream_t s2 = s;
-    if (pipe) {
-        if (!c->p2_stream && hipStreamCreateWithFlags(&c->p2_stream, hipStreamNonBlocking) != hipSuccess) return BSDB_EIO;
-        for (auto &e : c->pipe_ev)
-            if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return BSDB_EIO;
-        s2 = c->p2_stream;
-        HIP_OK(hipEventRecord(c->pipe_ev[4], s));  // the caller's earlier work
-        HIP_OK(hipStreamWaitEvent(s2, c->pipe_ev[4], 0));
-    }
-    const uint32_t p2_cus = pipe ? pipe_p2_cus(c) : 0;
-    a.scratch = c->cursor + nbuf * cur_per_buf;
-    a.cap = pp.cap;
-    a.nparts = pp.nparts;
-    a.nregions = pp.nmain;
-    a.region0 = 0;
-    a.ncopy = pp.nmain;
-    a.bin_shift = pp.bin_shift;
-    a.capb = pp.capb;
-    P2Layout L0{};
-    L0.cap = pp.cap;
-    L0.cap_tail = pp.cap_tail;
-    L0.nparts = pp.nparts;
-    L0.nmain = pp.nmain;
-    L0.ntail = pp.ntail;
-    L0.bshift = PART_SHIFT - pp.bin_shift;
-    L0.num_buckets = m;
-    L0.counts = counts;
-    uint64_t i = 0;  // launch of the call
-    for (uint64_t s0 = 0; s0 < n; s0 += J * chunk) {
-        // a span: keys [s0, s0 + ns) in jn launches (pipelined: one)
-        const uint64_t ns = std::min(J * chunk, n - s0), jn = (ns + chunk - 1) / chunk;
-        const bool last = s0 + ns >= n;
-        const uint32_t b = pipe ? (uint32_t)(i & 1) : 0;
-        // buffer b's ids, cursors, pass-2 plan and overflow flag
-        P1Args as = a;
-        as.ids = (uint16_t *)c->ids + b * ids_per_buf;
-        as.cursor = c->cursor + b * cur_per_buf;
-        as.overflow = c->overflow + 4 * b;
-        uint64_t *pref = c->p2_pref + b * (cur_per_buf + 1);
-        // the tail regions follow the span's main regions
-        uint16_t *const tail_ids = as.ids + set_elems;
-        uint32_t *const tail_cur = as.cursor + pp.nmain * pp.nparts;
-        P2Layout L = L0;
-        L.ids = as.ids;
-        L.cursor = as.cursor;
-        L.overflow = as.overflow;
-        as.n = ns;
-        if (var) {
-            as.offsets = offsets + s0;
-        } else {
-            as.keys = keys + s0 * key_len;
-            as.blob_bytes = pipe ? blob_bytes - s0 * key_len : ns * key_len;
-        }
-        if (pipe && i >= 2) HIP_OK(hipStreamWaitEvent(s, c->pipe_ev[2 + b], 0));  // pass 2 of chunk i - 2 read buffer b
-        HIP_OK(hipMemsetAsync(as.cursor, 0, sizeof(uint32_t) * cur_per_buf, s));
-        HIP_OK(hipMemsetAsync(as.overflow, 0, sizeof(uint32_t), s));
-        for (uint64_t j = 0; j < jn; ++j, ++i) {
-            const uint64_t k0 = s0 + j * chunk, nk = std::min(chunk, n - k0);
-            const bool first = k0 == 0, last_of_span = j + 1 == jn;
-            // launch j appends to the span's regions (as.ids, as.cursor)
-            P1Args ac = as;
-            ac.n = nk;
-            if (var) {
-                ac.offsets = offsets + k0;
-            } else {
-                ac.keys = keys + k0 * key_len;
-                // a window past the launch reads the next launch's bytes (the
-                // blob goes on): only the blob's end limits the persistent
-                // kernel, so a launch of whole tiles leaves no tail.  (A
-                // span's last launch keeps its own length, as a call of one
-                // launch always had.)
-                const bool to_end = pipe || !last_of_span;
-                ac.blob_bytes = to_end ? blob_bytes - k0 * key_len : nk * key_len;
-            }
-            ProfScope ps(c, s, 0, nk);
-            const uint64_t tiles = (nk + P1_TILE - 1) / P1_TILE;
-            // the keys from `done` on: to the bounds-checked kernel, in the
-            // tail regions
-            auto tail = [&](uint64_t done) {
-                P1Args at = ac;
-                at.n = nk - done;
-                at.ids = tail_ids;
-                at.cursor = tail_cur;
-                at.cap = pp.cap_tail;
-                at.nregions = pp.ntail;
-                if (var) {
-                    at.offsets = ac.offsets + done;
-                    k_pass1<SRC_VAR, EPI_PARTITION, 1, 0><<<(uint32_t)((at.n + P1_TILE - 1) / P1_TILE), P1_THREADS, 0, s>>>(at);
-                } else {
-                    at.keys = ac.keys + done * key_len;
-                    at.blob_bytes = at.n * key_len;
-                    launch_pass1<EPI_PARTITION>(at, false, key_len, (at.n + P1_TILE - 1) / P1_TILE, s, 0);
-                }
-            };
-            if (d13 && !sel.windowed) {
-                // full tiles to the persistent kernel, the rest (< 1 of its
-                // tiles) to the generic kernel
-                const uint64_t nfast = nk / sel.tile;
-                if (nfast) {
-                    const uint32_t grid = (uint32_t)std::min<uint64_t>(nfast, pp.grid_d13);
-                    sel.k<<<grid, sel.nt, 0, s>>>(ac, nfast);
-                }
-                if (nfast * sel.tile < nk) tail(nfast * sel.tile);
-            } else if (d13) {
-                // full tiles whose 16-byte windows stay inside the readable
-                // blob go to the persistent kernel (a key's window ends 16 - L
-                // bytes past it at most); the rest (< 2 of its tiles) to the
-                // bounds-checked kernel
-                const uint64_t dtile = sel.tile, over = 16 - key_len;
-                uint64_t nfast = 0;
-                if (ac.blob_bytes >= over) nfast = std::min(nk / dtile, ((ac.blob_bytes - over) / key_len) / dtile);
-                if (nfast) {
-                    uint32_t grid = (uint32_t)std::min<uint64_t>(nfast, pp.grid_d13);
-                    if (pipe && !first) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (uint32_t)c->num_cus - p2_cus));
-                    sel.k<<<grid, sel.nt, 0, s>>>(ac, nfast);
-                }
-                if (nfast * dtile < nk) tail(nfast * dtile);
-            } else {
-                launch_pass1<EPI_PARTITION>(ac, var, key_len, tiles, s, c->frontend);
-            }
-        }
-        if (pipe) {
-            HIP_OK(hipEventRecord(c->pipe_ev[b], s));  // pass 1 of chunk i done
-            HIP_OK(hipStreamWaitEvent(s2, c->pipe_ev[b], 0));
-        }
-        {
-            ProfScope ps(c, s2, 1, ns);
-            k_pass2_plan<<<1, SCAN_THREADS, 0, s2>>>(L, pref);
-            const uint32_t g2 = pipe && !last ? p2_cus : (uint32_t)c->num_cus;
-            k_pass2b<<<g2, P2_THREADS, 0, s2>>>(L, pref);
-        }
-        // an overflow anywhere in the span: pass 2 skipped all of it, and the
-        // whole span is recounted
-        if (var) {
-            k_overflow_fallback<SRC_VAR, 0><<<1024, P1_THREADS, 0, s2>>>(as);
-        } else {
-            k_overflow_fallback<SRC_FIXED_DIRECT, 0><<<1024, P1_THREADS, 0, s2>>>(as);
-        }
-        if (pipe) HIP_OK(hipEventRecord(c->pipe_ev[2 + b], s2));  // buffer b free again
-        if ((rc = launch_status())) return rc;
-    }
-    if (pipe) {
-        // the caller's stream continues after the last pass 2
-        HIP_OK(hipEventRecord(c->pipe_ev[5], s2));
-        HIP_OK(hipStreamWaitEvent(s, c->pipe_ev[5], 0));
-    }
-    return BSDB_OK;
-}
-
-int hash_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, uint64_t blob_bytes, uint32_t key_len,
-              uint64_t n, uint64_t seed, uint64_t *sig, hipStream_t s) {
-    if (n == 0) return BSDB_OK;
-    P1Args a{};
-    a.keys = keys;
-    a.offsets = offsets;
-    a.blob_bytes = blob_bytes;
-    a.key_len = key_len;
-    a.n = n;
-    a.seed = seed;
-    a.sig = sig;
-    launch_pass1<EPI_SIG>(a, offsets != nullptr, key_len, (n + P1_TILE - 1) / P1_TILE, s, c->frontend);
-    return launch_status();
-}
+// the histogram and hash stages (inside this namespace)
+#include "capi_hist.hip"
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -1211,7 +679,7 @@ int bsdb_dev_histogram_fixed(bsdb_ctx *c, const uint8_t *d_keys, uint32_t key_le
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OK(hipSetDevice(c->device));
     Ordered ord(c, pick(c, stream));
-    return histogram_impl(c, d_keys, nullptr, n * key_len, key_len, n, seed, m, d_counts, pick(c, stream));
+    return histogram_impl(c, d_keys, nullptr, n * key_len, key_len, n, seed, m, d_counts, hist_opts(c), pick(c, stream));
 }
 
 int bsdb_dev_histogram_var(bsdb_ctx *c, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_off,
@@ -1220,7 +688,7 @@ int bsdb_dev_histogram_var(bsdb_ctx *c, const uint8_t *d_blob, uint64_t blob_byt
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OK(hipSetDevice(c->device));
     Ordered ord(c, pick(c, stream));
-    return histogram_impl(c, d_blob, d_off, blob_bytes, 0, n, seed, m, d_counts, pick(c, stream));
+    return histogram_impl(c, d_blob, d_off, blob_bytes, 0, n, seed, m, d_counts, hist_opts(c), pick(c, stream));
 }
 
 static int edge_offsets_impl(bsdb_ctx *c, const uint32_t *d_counts, uint64_t m, uint64_t *d_E, void *stream);
@@ -1892,7 +1360,7 @@ static int host_histogram_fixed(bsdb_ctx *c, const uint8_t *h_keys, uint32_t key
         [&](FeedSlot &f, uint64_t k0, uint64_t k1) { return upload_fixed(c, f, h_keys, key_len, k0, k1); },
         [&](FeedSlot &f, uint64_t k0, uint64_t k1) {
             return histogram_impl(c, (const uint8_t *)f.buf[0], nullptr, (k1 - k0) * key_len, key_len, k1 - k0, seed, m,
-                                  d_counts, c->stream);
+                                  d_counts, hist_opts(c), c->stream);
         });
 }
 
@@ -1903,7 +1371,7 @@ static int host_histogram_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t
         [&](FeedSlot &f, uint64_t k0, uint64_t k1) { return upload_var(c, f, h_blob, h_off, k0, k1); },
         [&](FeedSlot &f, uint64_t k0, uint64_t k1) {
             return histogram_impl(c, (const uint8_t *)f.buf[0], (const uint64_t *)f.buf[1], h_off[k1] - h_off[k0], 0,
-                                  k1 - k0, seed, m, d_counts, c->stream);
+                                  k1 - k0, seed, m, d_counts, hist_opts(c), c->stream);
         });
 }
 

@@ -73,13 +73,9 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
         HIP_OK(dmalloc(&q, m * 4));
         counts_all.reset(q);
         HIP_OK(hipMemsetAsync(q, 0, m * 4, s));
-        const uint64_t saved_chunk = c->chunk_keys, saved_span = c->span_max;
-        c->chunk_keys = 1ULL << 30;
-        c->span_max = 1;  // a pass 2 per launch: the id workspace of one launch
+        // (a pass 2 per launch: the id workspace of one launch)
         const int hrc = histogram_impl(c, src.keys, src.off, src.blob_bytes, src.off ? 0 : src.key_len, n, 0, m,
-                                       (uint32_t *)q, s);
-        c->chunk_keys = saved_chunk;
-        c->span_max = saved_span;
+                                       (uint32_t *)q, HistOpts{1ULL << 30, 1}, s);
         HIP_OK(hipStreamSynchronize(s));
         (void)hipFree(c->ids);
         c->ids = nullptr;

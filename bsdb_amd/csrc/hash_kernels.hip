@@ -23,18 +23,12 @@
 
 #include <type_traits>
 
+#include "hist_geometry.hpp"  // tile and bin geometry: P1_*, PART_*, NCOPY, D13E_*, VARE_*
 #include "spooky_dev.hpp"
 
 namespace bsdb {
 
-constexpr int P1_THREADS = 512;
-constexpr int P1_KEYS_PER_THREAD = 16;
-constexpr int P1_TILE = P1_THREADS * P1_KEYS_PER_THREAD;  // 8192 keys per workgroup
 constexpr int STAGE_BYTES = 26624;                        // 2048 keys x 13 B
-constexpr int PART_SHIFT = 15;                            // 32768 buckets per partition
-constexpr int PART_BUCKETS = 1 << PART_SHIFT;
-constexpr int MAX_PARTS = 512;
-constexpr int NCOPY = 8;                                  // cursor/region copies (one per XCD)
 constexpr int P2_THREADS = 1024;
 
 enum Epi { EPI_PARTITION = 0, EPI_ATOMIC = 1, EPI_SIG = 2 };
@@ -69,8 +63,6 @@ struct P1Args {
     // the cursor atomics of lanes without a partition
     uint32_t *scratch;
 };
-constexpr uint32_t P1_SCRATCH_WG = 10240;
-constexpr uint32_t P1_SCRATCH_MAXWG = 2048;
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2), aligned(8)));
@@ -434,7 +426,7 @@ constexpr int D13_Q = 4;                          // keys per quarter
 constexpr int D13_NQ = P1_KEYS_PER_THREAD / D13_Q;  // quarters per tile
 
 // The production kernel above k_pass1_d13e's 288 bins, and its reference
-// point (BSDB_D13_VARIANT=2); only NT = 512 is built.  The round-1 epilogue,
+// point (BSDB_D13_VARIANT=2); only NT = D13_NT (512) is built.  The round-1 epilogue,
 // with its loads made unconditional and the epilogue run at raised wave
 // priority (the workgroup's critical path).
 template <int NT>
@@ -587,11 +579,7 @@ __global__ __launch_bounds__(NT, 4) void k_pass1_d13(P1Args a, uint64_t ntiles) 
 // A bin holds 128 ids (tile share 61 +- 8); a run that would not fit padded
 // (c > 120) or a full region raises the overflow flag and the chunk is
 // recounted with direct atomics.
-constexpr int D13E_NT = 1024;
 constexpr int D13E_NW = D13E_NT / 64;
-constexpr int D13E_TILE = D13E_NT * P1_KEYS_PER_THREAD;  // 16384
-constexpr int D13E_BIN_IDS = 36864;  // ids per bin buffer: nparts * capb (72 KiB, two buffers)
-constexpr int D13E_MAXP = 288;       // bins (capb >= 128 ids: tile share 57 +- 7.5 at 288 bins)
 constexpr uint16_t ID_PAD = 0xFFFF;                       // not a local id (ids are < 2^15)
 
 // VARIANT 13 (13-byte keys' default) = the cursor atomic as a range-checked
@@ -830,12 +818,7 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
 //    reserves its run in the XCD copy with one cursor atomic and its wave
 //    writes its bins out in 16-byte chunks (k_pass1_d13e's write-out); a
 //    second barrier frees the bins.  <= 144 bins of >= 2.25x their mean fill.
-constexpr int VARE_NT = 512;
 constexpr int VARE_NW = VARE_NT / 64;
-constexpr int VARE_NG = 8;                         // groups of 128 keys per wave per tile
-constexpr int VARE_TILE = VARE_NT * 2 * VARE_NG;   // 8192 keys
-constexpr int VARE_BIN_IDS = 18432;                // ids in the bins (36 KiB)
-constexpr int VARE_MAXP = 144;
 constexpr uint32_t VARE_PRE_VECS = 192;            // 16-B vectors per group prefetched (3 per lane)
 constexpr uint32_t VARE_STAGE_VECS = 288;          // 16-B vectors per wave stage (4.5 KiB)
 constexpr int VARE_STAGE_WORDS = VARE_STAGE_VECS * 4 + 20;  // + slack for the 17-dword key reads
