@@ -550,7 +550,7 @@ int spill_add_locked(bsdb_builder *b, const AddBatch &a, uint64_t n0) {
         if (kbytes) HIP_OK(hipMemcpyAsync(d_k, a.off ? a.keys + a.off[i0] : a.keys + i0 * a.key_len, kbytes, hipMemcpyHostToDevice, s));
         if (a.off) {
             HIP_OK(hipMemcpyAsync(d_o, a.off + i0, (k + 1) * 8, hipMemcpyHostToDevice, s));
-            k_rebase_offsets<<<grid_for(c, k + 1), 256, 0, s>>>(d_o, k + 1, (uint64_t)0 - a.off[i0]);
+            k_rebase_offsets<<<grid_for(c->num_cus, k + 1), 256, 0, s>>>(d_o, k + 1, (uint64_t)0 - a.off[i0]);
         }
         rc = a.off ? hash_impl(c, d_k, d_o, kbytes, 0, k, 0, (uint64_t *)d_sig, s)
                    : hash_impl(c, d_k, nullptr, kbytes, a.key_len, k, 0, (uint64_t *)d_sig, s);
@@ -636,12 +636,12 @@ int add_copy_device(bsdb_builder *b, const AddBatch &a, uint64_t n0, uint64_t kb
         if (a.uni != 0xFFFFFFFFu) {
             // one length (a kv.db partition of fixed-size keys): the offsets
             // are a formula, written on the device instead of copied
-            k_fill_offsets<<<grid_for(c, a.count), 256, 0, s>>>(dst, a.count, kb0, a.uni);
+            k_fill_offsets<<<grid_for(c->num_cus, a.count), 256, 0, s>>>(dst, a.count, kb0, a.uni);
             e = hipGetLastError();
         } else {
             e = hipMemcpyAsync(dst, a.off + 1, a.count * 8, hipMemcpyHostToDevice, s);
             if (e == hipSuccess) {
-                k_rebase_offsets<<<grid_for(c, a.count), 256, 0, s>>>(dst, a.count, kb0 - a.o0());
+                k_rebase_offsets<<<grid_for(c->num_cus, a.count), 256, 0, s>>>(dst, a.count, kb0 - a.o0());
                 e = hipGetLastError();
             }
         }
@@ -757,10 +757,8 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
     OutFile fo, fao;
     Populator pop_o, pop_a;
     void *d_addr = nullptr, *d_v8 = nullptr, *d_vl = nullptr;
-    void *slot_a[2] = {nullptr, nullptr};
-    size_t slot_a_bytes[2] = {0, 0};
-    void *sp_in = nullptr, *sp_out = nullptr;  // spill mode: a pass's uploaded segments, its compacted keys
-    size_t sp_in_bytes = 0, sp_out_bytes = 0;
+    DevBuf slot_a[2];
+    DevBuf sp_in, sp_out;  // spill mode: a pass's uploaded segments, its compacted keys
     bsdb_mph *p = nullptr;
     std::thread host_rel;  // the host record arrays' release, once the device copies took over
     // BSDB_BUILDER_PROFILE=1: the finish's phases on stderr
@@ -776,7 +774,8 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
         b->on_opened = nullptr;
         (void)hipStreamSynchronize(c->stream);
         if (host_rel.joinable()) host_rel.join();
-        for (void *q : {d_addr, d_v8, d_vl, slot_a[0], slot_a[1], sp_in, sp_out}) (void)hipFree(q);
+        for (void *q : {d_addr, d_v8, d_vl}) (void)hipFree(q);
+        for (DevBuf *q : {&slot_a[0], &slot_a[1], &sp_in, &sp_out}) q->free();
         pop_o.finish();
         pop_a.finish();
         if (prof && fo.map)
@@ -879,20 +878,20 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
             sink.positions = true;
             sink.job_bytes_per_key = b->approx ? 16 : 8;
             sink.prepare = [&](int sl, uint64_t nl) {
-                return b->approx ? grow(&slot_a[sl], &slot_a_bytes[sl], std::max<uint64_t>(nl, 1) * 8) : BSDB_OK;
+                return b->approx ? slot_a[sl].grow(std::max<uint64_t>(nl, 1) * 8) : BSDB_OK;
             };
             sink.job = [&](int sl, const uint64_t *d_slice, uint64_t nl, uint64_t e_lo) {
                 hipStream_t st = nullptr;
                 if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return BSDB_EIO;
-                k_slot_gather<<<grid_for(c, nl), 256, 0, st>>>(const_cast<uint64_t *>(d_slice), nl, dev_addr,
+                k_slot_gather<<<grid_for(c->num_cus, nl), 256, 0, st>>>(const_cast<uint64_t *>(d_slice), nl, dev_addr,
                                                                 b->addr_base, b->addr_stride, (const uint64_t *)d_v8,
                                                                 (const uint8_t *)d_vl,
-                                                                b->approx ? (uint64_t *)slot_a[sl] : nullptr);
+                                                                b->approx ? slot_a[sl].as<uint64_t>() : nullptr);
                 const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
                 (void)hipStreamDestroy(st);
                 if (!ok) return BSDB_EIO;
                 int r = write_slots(c->device, fo, d_slice, nl, e_lo, nullptr, nullptr);
-                if (!r && b->approx) r = write_slots(c->device, fao, (const uint64_t *)slot_a[sl], nl, e_lo, nullptr, nullptr);
+                if (!r && b->approx) r = write_slots(c->device, fao, slot_a[sl].as<const uint64_t>(), nl, e_lo, nullptr, nullptr);
                 return r;
             };
         } else {
@@ -935,9 +934,9 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
             uint64_t tot = 0;
             for (uint32_t k = s_a; k <= s_b && k < NSEG; ++k) tot += b->seg_sig[k].n;
             int r;
-            if ((r = grow(&sp_in, &sp_in_bytes, tot * 24 + 256)) || (r = grow(&sp_out, &sp_out_bytes, tot * 24 + 512)))
+            if ((r = sp_in.grow(tot * 24 + 256)) || (r = sp_out.grow(tot * 24 + 512)))
                 return r;
-            ulonglong2 *in_sig = (ulonglong2 *)sp_in, *out_sig = (ulonglong2 *)sp_out;
+            ulonglong2 *in_sig = sp_in.as<ulonglong2>(), *out_sig = sp_out.as<ulonglong2>();
             uint64_t *in_pos = (uint64_t *)(in_sig + tot), *out_pos = (uint64_t *)(out_sig + tot);
             unsigned long long *d_cnt = (unsigned long long *)(out_pos + tot);
             hipStream_t st = c->stream;
@@ -951,7 +950,7 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
             }
             HIP_OK(hipMemsetAsync(d_cnt, 0, 8, st));
             if (tot)
-                k_range_compact<<<grid_for(c, tot), 256, 0, st>>>(in_sig, in_pos, tot, (uint32_t)mult, (uint32_t)b_lo,
+                k_range_compact<<<grid_for(c->num_cus, tot), 256, 0, st>>>(in_sig, in_pos, tot, (uint32_t)mult, (uint32_t)b_lo,
                                                                   (uint32_t)b_hi, out_sig, out_pos, d_cnt);
             if ((r = launch_status())) return r;
             unsigned long long got = 0;

@@ -82,15 +82,14 @@ static int finalize_impl(bsdb_ctx *c, const Rccl *r, uint32_t *d_counts, uint64_
                          hipStream_t s) {
     int rc;
     const uint64_t nw = (m + 1) / 2;
-    if ((rc = grow(&c->pack, &c->pack_bytes, nw * 4))) return rc;
-    uint32_t *packed = (uint32_t *)c->pack;
-    k_pack16<<<grid_for(c, nw), 256, 0, s>>>(d_counts, m, packed);
+    if ((rc = c->pack.grow(nw * 4))) return rc;
+    uint32_t *packed = c->pack.as<uint32_t>();
+    k_pack16<<<grid_for(c->num_cus, nw), 256, 0, s>>>(d_counts, m, packed);
     if (r->all_reduce(packed, packed, nw, NCCL_UINT32, NCCL_SUM, (nccl_comm_t)c->comm, s) != 0) return BSDB_ECOMM;
     // unpack into a copy: the u32 retry below needs the local counts intact
-    uint32_t *global = (uint32_t *)c->g_counts;
-    if ((rc = grow(&c->g_counts, &c->g_counts_bytes, m * 4))) return rc;
-    global = (uint32_t *)c->g_counts;
-    k_unpack16<<<grid_for(c, m), 256, 0, s>>>(packed, m, global);
+    if ((rc = c->g_counts.grow(m * 4))) return rc;
+    uint32_t *global = c->g_counts.as<uint32_t>();
+    k_unpack16<<<grid_for(c->num_cus, m), 256, 0, s>>>(packed, m, global);
     if ((rc = edge_offsets_impl(c, global, m, d_E, s))) return rc;
     uint64_t total = 0;
     HIP_OK(hipMemcpyAsync(&total, d_E + m, 8, hipMemcpyDeviceToHost, s));
@@ -236,14 +235,14 @@ int multi_histogram(bsdb_multi *mc, uint64_t n, uint64_t *h_E, ShardFn &&shard) 
     for (int i = 0; i < k; ++i) {
         bsdb_ctx *c = mc->ctx[i];
         HIP_OK(hipSetDevice(c->device));
-        if ((rc = grow(&c->pack, &c->pack_bytes, ((m + 1) / 2) * 4))) return rc;
-        k_pack16<<<grid_for(c, (m + 1) / 2), 256, 0, c->stream>>>(mc->counts[i], m, (uint32_t *)c->pack);
+        if ((rc = c->pack.grow(((m + 1) / 2) * 4))) return rc;
+        k_pack16<<<grid_for(c->num_cus, (m + 1) / 2), 256, 0, c->stream>>>(mc->counts[i], m, c->pack.as<uint32_t>());
     }
     if (r->group_start() != 0) return BSDB_ECOMM;
     for (int i = 0; i < k; ++i) {
         bsdb_ctx *c = mc->ctx[i];
         (void)hipSetDevice(c->device);
-        if (r->all_reduce(c->pack, c->pack, (m + 1) / 2, NCCL_UINT32, NCCL_SUM, (nccl_comm_t)mc->comms[i], c->stream) != 0) {
+        if (r->all_reduce(c->pack.p, c->pack.p, (m + 1) / 2, NCCL_UINT32, NCCL_SUM, (nccl_comm_t)mc->comms[i], c->stream) != 0) {
             (void)r->group_end();
             return BSDB_ECOMM;
         }
@@ -255,9 +254,9 @@ int multi_histogram(bsdb_multi *mc, uint64_t n, uint64_t *h_E, ShardFn &&shard) 
             bsdb_ctx *c = mc->ctx[i];
             HIP_OK(hipSetDevice(c->device));
             if (!wide) {
-                if ((rc = grow(&c->g_counts, &c->g_counts_bytes, m * 4))) return rc;
-                k_unpack16<<<grid_for(c, m), 256, 0, c->stream>>>((const uint32_t *)c->pack, m, (uint32_t *)c->g_counts);
-                if ((rc = edge_offsets_impl(c, (const uint32_t *)c->g_counts, m, mc->E[i], c->stream))) return rc;
+                if ((rc = c->g_counts.grow(m * 4))) return rc;
+                k_unpack16<<<grid_for(c->num_cus, m), 256, 0, c->stream>>>(c->pack.as<const uint32_t>(), m, c->g_counts.as<uint32_t>());
+                if ((rc = edge_offsets_impl(c, c->g_counts.as<uint32_t>(), m, mc->E[i], c->stream))) return rc;
             } else {
                 if ((rc = edge_offsets_impl(c, mc->counts[i], m, mc->E[i], c->stream))) return rc;
             }

@@ -112,7 +112,7 @@ int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t
     if (per_cu < 1) return BSDB_OK;  // every workgroup must be resident
     const size_t sync_bytes = FU_SYNC_U64 * sizeof(uint64_t);
     const size_t ring_bytes = (size_t)FU_SLOTS * FU_SLOT_BYTES;
-    int rc = grow(&c->fu_ring, &c->fu_ring_bytes, ring_bytes + sync_bytes);
+    int rc = c->fu_ring.grow(ring_bytes + sync_bytes);
     if (rc) return rc;
     FusedArgs fa{};
     fa.keys = keys;
@@ -120,12 +120,12 @@ int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t
     fa.seed = seed;
     fa.mult = (uint32_t)(2 * m);
     fa.m = (uint32_t)m;
-    fa.ring = (uint8_t *)c->fu_ring;
-    fa.sync = (uint64_t *)((uint8_t *)c->fu_ring + ring_bytes);
-    fa.overflow = c->overflow;
+    fa.ring = c->fu_ring.as<uint8_t>();
+    fa.sync = (uint64_t *)(c->fu_ring.as<uint8_t>() + ring_bytes);
+    fa.overflow = c->overflow.as<uint32_t>();
     fa.counts = counts;
     HIP_OK(hipMemsetAsync(fa.sync, 0, sync_bytes, s));
-    HIP_OK(hipMemsetAsync(c->overflow, 0, sizeof(uint32_t), s));
+    HIP_OK(hipMemsetAsync(c->overflow.p, 0, sizeof(uint32_t), s));
     ++c->fu_launches;
     {
         ProfScope ps(c, s, 0, nsuper * per);
@@ -138,7 +138,7 @@ int fused13_impl(bsdb_ctx *c, const uint8_t *keys, uint64_t blob_bytes, uint64_t
     P1Args af = key_args(keys, nullptr, blob_bytes, 13, nsuper * per, seed);
     af.multiplier = 2 * m;
     af.counts = counts;
-    af.overflow = c->overflow;
+    af.overflow = c->overflow.as<uint32_t>();
     k_overflow_fallback<SRC_FIXED_DIRECT, 0><<<1024, P1_THREADS, 0, s>>>(af);
     if ((rc = launch_status())) return rc;
     *done = nsuper * per;
@@ -239,27 +239,26 @@ int histogram_impl(bsdb_ctx *c, const uint8_t *keys, const uint64_t *offsets, ui
     if (kern && hipOccupancyMaxActiveBlocksPerMultiprocessor(&in.wg_per_cu, kern, p.k.nt(), 0) != hipSuccess) in.wg_per_cu = 0;
     size_t total_b = 0;
     if (hipMemGetInfo(&in.free_bytes, &total_b) != hipSuccess) in.free_bytes = 0;
-    in.ids_bytes = c->ids_bytes;
+    in.ids_bytes = c->ids.bytes;
     hist_size(in, p);
     int rc;
-    if ((rc = grow(&c->ids, &c->ids_bytes, p.ids_bytes())) ||
-        (rc = grow((void **)&c->cursor, &c->cursor_bytes, p.cursor_bytes())) ||
-        (rc = grow((void **)&c->p2_pref, &c->p2_pref_bytes, p.prefix_bytes())))
+    if ((rc = c->ids.grow(p.ids_bytes())) || (rc = c->cursor.grow(p.cursor_bytes())) ||
+        (rc = c->p2_pref.grow(p.prefix_bytes())))
         return rc;
     // pipelined: pass 1 on the caller's stream, pass 2 on the context's second
     hipStream_t s2 = s;
     if (p.pipe && (rc = pipe_begin(c, s, &s2))) return rc;
-    a.scratch = c->cursor + p.nbuf * p.cur_per_buf();
+    a.scratch = c->cursor.as<uint32_t>() + p.nbuf * p.cur_per_buf();
     region_args(a, p);
     P2Layout L = pass2_layout(p, m, counts);
     for (uint64_t i = 0, nspans = p.spans(); i < nspans; ++i) {
         const HistSpan sp = p.span(i);
         const uint32_t b = sp.buf;
         // buffer b's ids, cursors, pass-2 plan and overflow flag
-        L.ids = a.ids = (uint16_t *)c->ids + b * p.ids_per_buf();
-        L.cursor = a.cursor = c->cursor + b * p.cur_per_buf();
-        L.overflow = a.overflow = c->overflow + 4 * b;
-        uint64_t *pref = c->p2_pref + b * (p.cur_per_buf() + 1);
+        L.ids = a.ids = c->ids.as<uint16_t>() + b * p.ids_per_buf();
+        L.cursor = a.cursor = c->cursor.as<uint32_t>() + b * p.cur_per_buf();
+        L.overflow = a.overflow = c->overflow.as<uint32_t>() + 4 * b;
+        uint64_t *pref = c->p2_pref.as<uint64_t>() + b * (p.cur_per_buf() + 1);
         if (p.pipe && i >= 2) HIP_OK(hipStreamWaitEvent(s, c->pipe_ev[2 + b], 0));  // pass 2 of chunk i - 2 read buffer b
         HIP_OK(hipMemsetAsync(a.cursor, 0, sizeof(uint32_t) * p.cur_per_buf(), s));
         HIP_OK(hipMemsetAsync(a.overflow, 0, sizeof(uint32_t), s));

@@ -200,7 +200,7 @@ int mph_build_index(bsdb_ctx *c, uint64_t n, uint32_t width, const uint64_t *h_a
              chk(hipMemcpyAsync(vl, h_vlen, n, hipMemcpyHostToDevice, c->stream), "H2D vlen", __LINE__) &&
              chk(hipMemsetAsync(index_a, 0, nn * 8, c->stream), "memset index_a", __LINE__);
     if (ok && n) {
-        k_index_scatter<<<grid_for(c, n), 256, 0, c->stream>>>((const int64_t *)rank, (const uint64_t *)addr, n, 0, n,
+        k_index_scatter<<<grid_for(c->num_cus, n), 256, 0, c->stream>>>((const int64_t *)rank, (const uint64_t *)addr, n, 0, n,
                                                                 (uint64_t *)index, (const uint64_t *)v8,
                                                                 (const uint8_t *)vl, (uint8_t *)index_a);
         ok = chk(hipGetLastError(), "k_index_scatter", __LINE__);
@@ -234,10 +234,10 @@ int mph_lookup_host(bsdb_mph *p, uint64_t n, int check, int64_t *h_out, Upload &
     const MphView v{p->E, p->values, p->sigbits, p->n, (uint32_t)(2 * p->m), p->width};
     int rc = upload_and_hash.template run<true>(c, n, [&](FeedSlot &f, uint64_t k0, uint64_t k1, const uint64_t *d_sig) {
         const uint64_t nk = k1 - k0;
-        int r2 = grow(&f.buf[7], &f.cap[7], nk * 8);
+        int r2 = f.buf[7].grow(nk * 8);
         if (r2) return r2;
-        k_lookup<<<grid_for(c, nk), 256, 0, c->stream>>>(v, d_sig, nk, check, (int64_t *)f.buf[7]);
-        HIP_OK(hipMemcpyAsync(h_out + k0, f.buf[7], nk * 8, hipMemcpyDeviceToHost, c->stream));
+        k_lookup<<<grid_for(c->num_cus, nk), 256, 0, c->stream>>>(v, d_sig, nk, check, f.buf[7].as<int64_t>());
+        HIP_OK(hipMemcpyAsync(h_out + k0, f.buf[7].p, nk * 8, hipMemcpyDeviceToHost, c->stream));
         return launch_status();
     });
     if (rc) return rc;
@@ -257,12 +257,12 @@ struct FixedKeys {
             [&](FeedSlot &f, uint64_t k0, uint64_t k1) { return upload_fixed(c, f, keys, key_len, k0, k1); },
             [&](FeedSlot &f, uint64_t k0, uint64_t k1) {
                 const uint64_t nk = k1 - k0;
-                int rc = grow(&f.buf[6], &f.cap[6], nk * 16);
+                int rc = f.buf[6].grow(nk * 16);
                 if (rc) return rc;
-                if ((rc = hash_impl(c, (const uint8_t *)f.buf[0], nullptr, nk * key_len, key_len, nk, 0,
-                                    (uint64_t *)f.buf[6], c->stream)))
+                if ((rc = hash_impl(c, f.buf[0].as<const uint8_t>(), nullptr, nk * key_len, key_len, nk, 0,
+                                    f.buf[6].as<uint64_t>(), c->stream)))
                     return rc;
-                return then(f, k0, k1, (const uint64_t *)f.buf[6]);
+                return then(f, k0, k1, f.buf[6].as<const uint64_t>());
             });
     }
 };
@@ -277,12 +277,12 @@ struct VarKeys {
             [&](FeedSlot &f, uint64_t k0, uint64_t k1) { return upload_var(c, f, blob, off, k0, k1); },
             [&](FeedSlot &f, uint64_t k0, uint64_t k1) {
                 const uint64_t nk = k1 - k0;
-                int rc = grow(&f.buf[6], &f.cap[6], nk * 16);
+                int rc = f.buf[6].grow(nk * 16);
                 if (rc) return rc;
-                if ((rc = hash_impl(c, (const uint8_t *)f.buf[0], (const uint64_t *)f.buf[1], off[k1] - off[k0], 0, nk, 0,
-                                    (uint64_t *)f.buf[6], c->stream)))
+                if ((rc = hash_impl(c, f.buf[0].as<const uint8_t>(), f.buf[1].as<const uint64_t>(), off[k1] - off[k0], 0, nk, 0,
+                                    f.buf[6].as<uint64_t>(), c->stream)))
                     return rc;
-                return then(f, k0, k1, (const uint64_t *)f.buf[6]);
+                return then(f, k0, k1, f.buf[6].as<const uint64_t>());
             });
     }
 };
@@ -434,19 +434,19 @@ int index_put(bsdb_index *ix, const Keys &keys, uint64_t count, const uint64_t *
     return keys.template run<true>(c, count, [&](FeedSlot &f, uint64_t k0, uint64_t k1, const uint64_t *d_sig) {
         const uint64_t nk = k1 - k0;
         int rc;
-        if ((rc = grow(&f.buf[2], &f.cap[2], nk * 8)) || (rc = grow(&f.buf[7], &f.cap[7], nk * 8))) return rc;
+        if ((rc = f.buf[2].grow(nk * 8)) || (rc = f.buf[7].grow(nk * 8))) return rc;
         // the record payloads go on the compute stream (they are not needed
         // before the scatter, and it keeps the slot's buffers in one order)
-        HIP_OK(hipMemcpyAsync(f.buf[2], h_addr + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(f.buf[2].p, h_addr + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
         if (ix->approx) {
-            if ((rc = grow(&f.buf[3], &f.cap[3], nk * 8)) || (rc = grow(&f.buf[4], &f.cap[4], nk))) return rc;
-            HIP_OK(hipMemcpyAsync(f.buf[3], h_value8 + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_OK(hipMemcpyAsync(f.buf[4], h_vlen + k0, nk, hipMemcpyHostToDevice, c->stream));
+            if ((rc = f.buf[3].grow(nk * 8)) || (rc = f.buf[4].grow(nk))) return rc;
+            HIP_OK(hipMemcpyAsync(f.buf[3].p, h_value8 + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(f.buf[4].p, h_vlen + k0, nk, hipMemcpyHostToDevice, c->stream));
         }
-        k_lookup<<<grid_for(c, nk), 256, 0, c->stream>>>(v, d_sig, nk, 1, (int64_t *)f.buf[7]);
-        k_index_scatter<<<grid_for(c, nk), 256, 0, c->stream>>>(
-            (const int64_t *)f.buf[7], (const uint64_t *)f.buf[2], nk, start, len, ix->d_index,
-            ix->approx ? (const uint64_t *)f.buf[3] : nullptr, ix->approx ? (const uint8_t *)f.buf[4] : nullptr,
+        k_lookup<<<grid_for(c->num_cus, nk), 256, 0, c->stream>>>(v, d_sig, nk, 1, f.buf[7].as<int64_t>());
+        k_index_scatter<<<grid_for(c->num_cus, nk), 256, 0, c->stream>>>(
+            f.buf[7].as<const int64_t>(), f.buf[2].as<const uint64_t>(), nk, start, len, ix->d_index,
+            ix->approx ? f.buf[3].as<const uint64_t>() : nullptr, ix->approx ? f.buf[4].as<const uint8_t>() : nullptr,
             ix->approx ? ix->d_index_a : nullptr);
         return launch_status();
     });

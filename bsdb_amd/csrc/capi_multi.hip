@@ -227,7 +227,7 @@ int multi_build(bsdb_multi *mc, uint64_t n, uint32_t width, const uint64_t *h_ad
             HIP_OK(hipSetDevice(c->device));
             Ordered ord(c, c->stream);
             if ((r = hash_shard(c, d.lo, d.hi, sig))) return r;
-            if (index && nd) k_iota64<<<grid_for(c, nd), 256, 0, c->stream>>>(perm, nd);
+            if (index && nd) k_iota64<<<grid_for(c->num_cus, nd), 256, 0, c->stream>>>(perm, nd);
             if ((r = launch_status())) return r;
         }
         if ((r = bsdb_dev_partition_owners(c, sig, perm, nd, m, G, d.sig_g, perm_g, d.cnt, c->stream))) return r;
@@ -247,10 +247,10 @@ int multi_build(bsdb_multi *mc, uint64_t n, uint32_t width, const uint64_t *h_ad
             HIP_OK(hipMemcpyAsync(vl, h_vlen + d.lo, nd, hipMemcpyHostToDevice, c->stream));
         }
         if (nd) {
-            k_gather<<<grid_for(c, nd), 256, 0, c->stream>>>(perm_g, a, nd, d.addr_g);
+            k_gather<<<grid_for(c->num_cus, nd), 256, 0, c->stream>>>(perm_g, a, nd, d.addr_g);
             if (approx) {
-                k_gather<<<grid_for(c, nd), 256, 0, c->stream>>>(perm_g, v8, nd, d.v8_g);
-                k_gather<<<grid_for(c, nd), 256, 0, c->stream>>>(perm_g, vl, nd, d.vl_g);
+                k_gather<<<grid_for(c->num_cus, nd), 256, 0, c->stream>>>(perm_g, v8, nd, d.v8_g);
+                k_gather<<<grid_for(c->num_cus, nd), 256, 0, c->stream>>>(perm_g, vl, nd, d.vl_g);
             }
         }
         if ((r = launch_status())) return r;

@@ -77,9 +77,7 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
         const int hrc = histogram_impl(c, src.keys, src.off, src.blob_bytes, src.off ? 0 : src.key_len, n, 0, m,
                                        (uint32_t *)q, HistOpts{1ULL << 30, 1}, s);
         HIP_OK(hipStreamSynchronize(s));
-        (void)hipFree(c->ids);
-        c->ids = nullptr;
-        c->ids_bytes = 0;
+        c->ids.free();
         if (hrc) return hrc;
         gsrc.counts_all = (const uint32_t *)q;
     }
@@ -87,11 +85,8 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
     // it: released, so the pass count below sees their memory as free (they
     // grow back to this build's pass size)
     HIP_OK(hipStreamSynchronize(s));
-    for (void **q : {&c->g_sorted, &c->g_pay}) {
-        (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->g_sorted_bytes = c->g_pay_bytes = 0;
+    c->g_sorted.free();
+    c->g_pay.free();
     if (passes == 0) {
         // the fewest passes whose working set fits 85 % of the free HBM (the
         // solver scratch and the per-bucket arrays come on top: ~10 GB)
@@ -107,8 +102,7 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
     if (width) HIP_OK(hipMemsetAsync(d_sigbits, 0, ((n * width + 63) / 64 + 1) * 8, s));
     // two device slice buffers; the copy-out of pass p's slots runs on a
     // thread of its own (own stream) while pass p+1 solves into the other
-    void *slice[2] = {nullptr, nullptr};
-    size_t slice_bytes[2] = {0, 0};
+    DevBuf slice[2];
     std::thread copier[2];
     int copy_rc[2] = {BSDB_OK, BSDB_OK};
     auto join = [&](int i) {
@@ -121,7 +115,7 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
             if (!rc) rc = r;
         }
         (void)hipSetDevice(c->device);
-        for (void *q : slice) (void)hipFree(q);
+        for (DevBuf &q : slice) q.free();
         return rc;
     };
     uint64_t e_lo = 0;
@@ -139,9 +133,9 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
             ixo.idx_lo = e_lo;
             ixo.slots = [&](uint64_t nl) -> uint64_t * {
                 if (join(sl)) return nullptr;  // the copy out of this buffer (pass p-2) is done
-                if (grow(&slice[sl], &slice_bytes[sl], std::max<uint64_t>(nl, 1) * 8)) return nullptr;
+                if (slice[sl].grow(std::max<uint64_t>(nl, 1) * 8)) return nullptr;
                 if (sink.prepare && sink.prepare(sl, nl)) return nullptr;
-                return (uint64_t *)slice[sl];
+                return slice[sl].as<uint64_t>();
             };
         }  // (neither: the structure only)
         uint64_t nl = 0;
@@ -159,7 +153,7 @@ int passes_build(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t width, uin
         if (prof) fprintf(stderr, "[bsdb passes] pass %u: %llu keys, start %.3f s, built in %.3f s\n", p,
                           (unsigned long long)nl, t_pass, since() - t_pass);
         if (sink.slices() && nl) {  // gov_build_impl returned after the device finished
-            const uint64_t *src_slots = (const uint64_t *)slice[sl];
+            const uint64_t *src_slots = slice[sl].as<const uint64_t>();
             const int dev = c->device;
             const uint64_t lo = e_lo;
             copy_rc[sl] = BSDB_OK;

@@ -17,7 +17,7 @@ struct VerifyWindow {
 
 void verify_launch(bsdb_ctx *c, const MphView &v, const VerifyArgs &a, hipStream_t s) {
     if (!a.n) return;
-    const uint32_t grid = grid_for(c, a.n);
+    const uint32_t grid = grid_for(c->num_cus, a.n);
     if (a.off)
         k_verify_var<<<grid, 256, 0, s>>>(v, a);
     else if (a.key_len == 13)
@@ -39,7 +39,7 @@ int dev_verify(bsdb_ctx *c, const uint8_t *d_keys, const uint64_t *d_off, uint64
     HIP_OK(hipSetDevice(c->device));
     hipStream_t s = pick(c, stream);
     unsigned long long *out = (unsigned long long *)d_out;
-    k_verify_structure<<<grid_for(c, m + 1), 256, 0, s>>>(d_E, m, n, out);
+    k_verify_structure<<<grid_for(c->num_cus, m + 1), 256, 0, s>>>(d_E, m, n, out);
     const MphView v{d_E, d_values, d_sigbits, n, (uint32_t)(2 * m), width};
     VerifyArgs a{};
     a.keys = d_keys;
@@ -143,7 +143,7 @@ struct VerifyRun {
         Ordered ord(c, c->stream);
         if (dmalloc(&d_out, BSDB_VERIFY_WORDS * 8) != hipSuccess) return BSDB_ENOMEM;
         HIP_OK(hipMemsetAsync(d_out, 0, BSDB_VERIFY_WORDS * 8, c->stream));
-        k_verify_structure<<<grid_for(c, p->m + 1), 256, 0, c->stream>>>(p->E, p->m, n, d_out);
+        k_verify_structure<<<grid_for(c->num_cus, p->m + 1), 256, 0, c->stream>>>(p->E, p->m, n, d_out);
         int rc = launch_status();
         if (rc) return rc;
         uint64_t flags = 0;
@@ -203,23 +203,23 @@ struct VerifyRun {
             },
             [&](FeedSlot &f, uint64_t k0, uint64_t k1) {
                 const uint64_t nk = k1 - k0;
-                int r2 = grow(&f.buf[2], &f.cap[2], nk * 8);
+                int r2 = f.buf[2].grow(nk * 8);
                 if (r2) return r2;
-                HIP_OK(hipMemcpyAsync(f.buf[2], h_addr + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
+                HIP_OK(hipMemcpyAsync(f.buf[2].p, h_addr + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
                 if (approx) {
-                    if ((r2 = grow(&f.buf[3], &f.cap[3], nk * 8)) || (r2 = grow(&f.buf[4], &f.cap[4], nk))) return r2;
-                    HIP_OK(hipMemcpyAsync(f.buf[3], h_value8 + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
-                    HIP_OK(hipMemcpyAsync(f.buf[4], h_vlen + k0, nk, hipMemcpyHostToDevice, c->stream));
+                    if ((r2 = f.buf[3].grow(nk * 8)) || (r2 = f.buf[4].grow(nk))) return r2;
+                    HIP_OK(hipMemcpyAsync(f.buf[3].p, h_value8 + k0, nk * 8, hipMemcpyHostToDevice, c->stream));
+                    HIP_OK(hipMemcpyAsync(f.buf[4].p, h_vlen + k0, nk, hipMemcpyHostToDevice, c->stream));
                 }
                 VerifyArgs a{};
-                a.keys = (const uint8_t *)f.buf[0];
-                a.off = h_off ? (const uint64_t *)f.buf[1] : nullptr;
+                a.keys = f.buf[0].as<const uint8_t>();
+                a.off = h_off ? f.buf[1].as<const uint64_t>() : nullptr;
                 a.blob_bytes = h_off ? h_off[k1] - h_off[k0] : nk * key_len;
                 a.n = nk;
                 a.key_len = key_len;
-                a.addr = (const uint64_t *)f.buf[2];
-                a.value8 = approx ? (const uint64_t *)f.buf[3] : nullptr;
-                a.vlen = approx ? (const uint8_t *)f.buf[4] : nullptr;
+                a.addr = f.buf[2].as<const uint64_t>();
+                a.value8 = approx ? f.buf[3].as<const uint64_t>() : nullptr;
+                a.vlen = approx ? f.buf[4].as<const uint8_t>() : nullptr;
                 a.start = win.start;
                 a.len = win.len;
                 a.index = win.d_index;

@@ -22,28 +22,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gov_geometry.hpp"
 #include "mph_kernels.hip"
 #include "spooky_dev.hpp"
 
 namespace bsdb {
 
-#ifndef GOV_THREADS
-#define GOV_THREADS 512  // workgroup size of the solver
-#endif
-constexpr int GS_THREADS = GOV_THREADS;
-// Two solver workgroups per CU (LDS <= 80 KiB each): one's single-wave
-// phases (greedy, BFS, FVS selection) overlap the other's.  4.2 sigma above
-// the mean bucket; larger buckets (~1e-5 of them) take the global-slab path.
-#ifndef GOV_PER_CU
-#define GOV_PER_CU 2
-#endif
-#ifndef GOV_CMAX
-#define GOV_CMAX 1664
-#endif
-// (GOV_PER_CU / GOV_CMAX other than 2 / 1664: measurement builds only,
-// tools/build_variant.sh, with BSDB_PROBE_BUCKET_SIZE)
-constexpr int GS_PER_CU = GOV_PER_CU;
-constexpr int GS_CMAX = GOV_CMAX;    // keys per bucket solved in LDS (expected ~1500, sigma ~39)
 constexpr int GS_NVMAX = GS_CMAX + GS_CMAX / 8;   // > vertex_offset span of GS_CMAX keys (1872)
 constexpr int GS_TINY = 12;      // brute-force buckets (only in sets of < ~1500 keys)
 #ifndef GOV_GJ_FOLLOW
@@ -71,20 +55,7 @@ __host__ __device__ constexpr size_t gj_panel_words(uint32_t n) {
 #define GOV_PICK_REPS 24
 #endif
 constexpr int GS_WMAX = (GS_CMAX + 1 + 63) / 64;  // words per bit-sliced row
-// Oversized buckets (adversarial or skewed key sets: > GS_CMAX keys, 14 sigma
-// above the mean for random keys) are solved by the same code with its state
-// in a per-workgroup slab of global memory, up to GB_CMAX keys.
-constexpr int GB_CMAX = 16384;  // a power of two (the bitonic sort's padding)
-// Oversized buckets up to GM_CMAX keys (every one of a random key set: the
-// largest of C4's 8.8 M buckets holds ~1 720) are solved with their state in
-// LDS by k_gov_solve_mid, one workgroup per CU; only larger (adversarial)
-// buckets take the global-slab kernel, whose every state access goes to L2.
-constexpr int GM_CMAX = 2048;
 constexpr int GB_THREADS = 256;  // sort of an oversized bucket
-// FVS: most heavy hinges of a block (a larger set falls back to Gauss-Jordan
-// over the whole block).  SolveArgs::fvs_max may lower it (tests force the
-// fallback with it); the result is the block's unique solution either way.
-constexpr uint32_t FVS_NH_MAX = 380;
 // FVS blocks whose heavy system is singular but consistent: at most NB_MAX
 // null vectors are reduced in place (more fall back to Gauss-Jordan over the
 // whole block, which reaches the same solution)
@@ -135,7 +106,6 @@ __global__ __launch_bounds__(256) void k_bucket_scatter(const uint64_t *sig, uin
 // bucket with one cursor atomic and places each key at its LDS rank in that
 // run (scatter).  The order inside a bucket stays arbitrary until
 // k_bucket_sort, as with the per-key atomics.
-constexpr uint32_t SMALL_NB = 4096, SMALL_KPT = 16, SMALL_CHUNK = 256 * SMALL_KPT;
 
 __global__ __launch_bounds__(256) void k_bucket_count_small(const uint64_t *sig, uint64_t n, uint32_t mult, uint32_t b0,
                                                             uint32_t nb, uint32_t *counts) {
@@ -201,7 +171,6 @@ __global__ __launch_bounds__(256) void k_bucket_scatter_small(const uint64_t *si
 // in a share) raises *flag before its half could carry into its neighbour:
 // k_bucket_count_redo then recounts with per-key atomics and the scatter
 // falls back to cursor atomics.
-constexpr uint32_t MID_NB = 80000, MID_THREADS = 1024;
 
 __global__ __launch_bounds__(MID_THREADS) void k_bucket_count_mid(const uint64_t *sig, uint64_t n, uint32_t mult,
                                                                   uint32_t b0, uint32_t nb, uint16_t *cw,
@@ -2817,8 +2786,6 @@ __global__ __launch_bounds__(256) void k_verify_ranks(MphView v, const uint64_t 
 __device__ __forceinline__ uint32_t owner_of(uint32_t b, uint64_t m, uint32_t G) {
     return (uint32_t)((((uint64_t)b + 1) * G - 1) / m);
 }
-
-constexpr int OWN_MAXR = 64;
 
 __global__ __launch_bounds__(256) void k_owner_count(const uint64_t *sig, uint64_t n, uint32_t mult, uint64_t m,
                                                      uint32_t G, unsigned long long *counts) {

@@ -362,6 +362,76 @@ def test_range_builds_sum_to_full_build(ctx):
     np.testing.assert_array_equal(u64(Ss)[: sb.size], sb)
 
 
+@pytest.fixture(scope="module")
+def large_class_sigs():
+    """300 000 random signatures of a structure on 121 500 000 keys (m = 81 001 buckets), with their buckets."""
+    n_global = 121_500_000
+    m = O.num_buckets(n_global)
+    assert m == 81_001
+    sig = np.random.default_rng(20).integers(0, 1 << 64, (300_000, 2), dtype=np.uint64)
+    return n_global, m, sig, O.buckets(sig, m).astype(np.int64)
+
+
+@pytest.mark.parametrize("b_lo,b_hi", [(0, 81_001), (500, 80_600)])
+def test_large_range_class_matches_oracle(ctx, large_class_sigs, b_lo, b_hi):
+    """A range of more than MID_NB = 80 000 buckets built from signatures: counted and scattered with per-key
+    atomics (k_bucket_count / k_bucket_scatter), the whole structure and an interior range with e_lo > 0;
+    E, values, checksum bits and ranks bit-identical to the oracle's range build."""
+    n_global, m, sig, b_of = large_class_sigs
+    width = 4
+    part = np.ascontiguousarray(sig[(b_of >= b_lo) & (b_of < b_hi)])
+    e_lo = int((b_of < b_lo).sum())
+    # the kernels index counts[bucket - b_lo] unchecked
+    pb = O.buckets(part, m)
+    assert b_hi - b_lo > 80_000 and b_hi <= m and pb.min() >= b_lo and pb.max() < b_hi
+    vw, sw = int(O.lib().bo_values_words(n_global)), (n_global * width + 63) // 64 + 1
+    E, vals, sb = np.zeros(m + 1, np.uint64), np.zeros(vw, np.uint64), np.zeros(sw, np.uint64)
+    assert O.gov_build_range(part, n_global, b_lo, b_hi, e_lo, width, E, vals, sb, THREADS) == 0
+    dE = torch.zeros(m + 1, dtype=torch.int64, device="cuda")
+    dv = torch.zeros(vw, dtype=torch.int64, device="cuda")
+    ds = torch.zeros(sw, dtype=torch.int64, device="cuda")
+    rk = torch.zeros(part.shape[0], dtype=torch.int64, device="cuda")
+    ctx.gov_build_range(dev(part.view(np.int64)), n_global, b_lo, b_hi, e_lo, width, dE, dv, ds, rank=rk)
+    np.testing.assert_array_equal(u64(dE), E)
+    np.testing.assert_array_equal(u64(dv), vals)
+    np.testing.assert_array_equal(u64(ds), sb)
+    E_look = E.copy()
+    E_look[b_hi] = max(int(E_look[b_hi]), e_lo + part.shape[0])  # (an interior range leaves E[b_hi] to the next one)
+    np.testing.assert_array_equal(rk.cpu().numpy(), O.lookup_batch(part, n_global, E_look, vals, width, sb, False))
+
+
+def test_window_build_leaves_guard_words(ctx):
+    """The middle range of the 600 000-key, 3-range shape built into windows that sit between 64 sentinel words
+    on both sides: no sentinel changes, and the windows equal the slices of the range build into full-size arrays."""
+    from bsdb_amd.native import range_windows
+    n, width, G, g, guard = 600_000, 5, 3, 1, 64
+    sig = O.hash_fixed_mt(O.gen_keys13(21, n), 13, THREADS)
+    m = n // 1500 + 1
+    grouped, counts = ctx.partition_owners(dev(sig.view(np.int64)), m, G)[::2]
+    b_lo, b_hi, e_lo = g * m // G, (g + 1) * m // G, counts[0]
+    part = grouped[e_lo: e_lo + counts[g]].contiguous()
+    v0, vw, s0, sw = range_windows(n, width, e_lo, counts[g])
+    full = [torch.zeros(k, dtype=torch.int64, device="cuda")
+            for k in (m + 1, int(O.lib().bo_values_words(n)), (n * width + 63) // 64 + 1)]
+    rk_full = torch.zeros(counts[g], dtype=torch.int64, device="cuda")
+    ctx.gov_build_range(part, n, b_lo, b_hi, e_lo, width, *full, rank=rk_full)
+    sentinel = 0x5A5A5A5A5A5A5A5A
+    bufs, wins = [], []
+    for words in (b_hi - b_lo + 1, vw, sw):
+        buf = torch.full((guard + words + guard,), sentinel, dtype=torch.int64, device="cuda")
+        buf[guard: guard + words] = 0
+        bufs.append(buf)
+        wins.append(buf[guard: guard + words])
+    rk = torch.zeros(counts[g], dtype=torch.int64, device="cuda")
+    ctx.gov_build_window(part, n, b_lo, b_hi, e_lo, width, wins[0], wins[1], v0, wins[2], s0, rank=rk)
+    torch.cuda.synchronize()
+    for buf, win, whole, first in zip(bufs, wins, full, (b_lo, v0, s0)):
+        assert torch.all(buf[:guard] == sentinel) and torch.all(buf[-guard:] == sentinel)
+        assert torch.equal(win, whole[first: first + win.numel()])
+        assert torch.count_nonzero(whole) == torch.count_nonzero(win)  # (the windows hold every word the range wrote)
+    assert torch.equal(rk, rk_full)
+
+
 def test_rccl_finalize_single_rank(ctx):
     """B4: the histogram all-reduce + scan inside the library (RCCL, one rank)."""
     from bsdb_amd.native import Context

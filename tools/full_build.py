@@ -4,6 +4,7 @@ signatures (A3) -> GOV build (A5/A6/A8/A11) -> ranks (A12) -> index scatter
 
     python tools/full_build.py [--n KEYS] [--width 4] [--approx]"""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -55,6 +56,9 @@ def main():
                             "total_ms": sum(st), "wall_s": wall, "keys_per_s": n / wall}
         print(json.dumps(res[f"rep{rep}"]), file=sys.stderr, flush=True)
         assert torch.equal(torch.sort(rank).values, torch.arange(n, device="cuda")), "ranks not a bijection"
+    # the last build's outputs, to compare two libraries: sha256 of E, values and the checksum bits
+    res["sha256"] = {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                     for k, t in (("E", E), ("values", values), ("sigbits", sigbits)) if t is not None}
     print(json.dumps(res))
 
 
