@@ -6,7 +6,8 @@
 // grown to the call's size), so a caller can capture them in a hipGraph.
 // The stages live in files included here: capi_hist.hip (histogram, with its
 // plan hist_plan.hpp), capi_gov.hip (GOV build, with its plan gov_plan.hpp),
-// capi_comm / mph / multi / passes / builder / kv / verify.hip.
+// capi_comm / mph / multi / passes / builder / kv / verify.hip, capi_dup.hip
+// (which keys are duplicates, with its plan dup_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -42,8 +43,10 @@
 #include "mph_kernels.hip"
 #include "gov_kernels.hip"
 #include "verify_kernels.hip"
+#include "dup_kernels.hip"
 #include "hist_plan.hpp"
 #include "gov_plan.hpp"
+#include "dup_plan.hpp"
 
 using namespace bsdb;
 
@@ -1031,3 +1034,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_builder.hip"
 #include "capi_kv.hip"
 #include "capi_verify.hip"
+#include "capi_dup.hip"

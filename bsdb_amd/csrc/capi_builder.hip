@@ -749,6 +749,54 @@ int close_out(OutFile &o) {
     return ok ? BSDB_OK : BSDB_EFILE;
 }
 
+// Spill mode: pass p's keys are those of the 256 host segments that can hold
+// its buckets [b_lo, b_hi) -- the segment is sig0's top byte and the bucket is
+// monotone in sig0 (CBHS:129-138, 900, 965), so a contiguous run of segments,
+// the two at its ends shared with the neighbouring passes -- uploaded into
+// sp_in and compacted to the range in sp_out on the device; *pos: each key's
+// add position.  The PassSink::source of the finish and of the duplicate
+// finder (capi_dup.hip); sp_in / sp_out outlive it.
+constexpr uint64_t SPILL_SOURCE_BYTES_PER_KEY = 2 * 24 + 8;
+std::function<int(uint64_t, uint64_t, GovSrc &, const uint64_t **)> spill_source(bsdb_builder *b, DevBuf &sp_in,
+                                                                                 DevBuf &sp_out) {
+    bsdb_ctx *c = b->c;
+    const uint64_t mult = 2 * (b->n / BUCKET_SIZE + 1);
+    return [b, c, mult, &sp_in, &sp_out](uint64_t b_lo, uint64_t b_hi, GovSrc &ps, const uint64_t **pos) -> int {
+        auto x_first = [&](uint64_t bk) { return (((unsigned __int128)bk << 64) + mult - 1) / mult; };  // first sig0 >>> 1 of bucket bk
+        const uint32_t s_a = (uint32_t)(x_first(b_lo) >> 55), s_b = (uint32_t)((x_first(b_hi) - 1) >> 55);
+        uint64_t tot = 0;
+        for (uint32_t k = s_a; k <= s_b && k < NSEG; ++k) tot += b->seg_sig[k].n;
+        int r;
+        if ((r = sp_in.grow(tot * 24 + 256)) || (r = sp_out.grow(tot * 24 + 512)))
+            return r;
+        ulonglong2 *in_sig = sp_in.as<ulonglong2>(), *out_sig = sp_out.as<ulonglong2>();
+        uint64_t *in_pos = (uint64_t *)(in_sig + tot), *out_pos = (uint64_t *)(out_sig + tot);
+        unsigned long long *d_cnt = (unsigned long long *)(out_pos + tot);
+        hipStream_t st = c->stream;
+        uint64_t at = 0;
+        for (uint32_t k = s_a; k <= s_b && k < NSEG; ++k) {
+            const uint64_t kn = b->seg_sig[k].n;
+            if (!kn) continue;
+            HIP_OK(hipMemcpyAsync(in_sig + at, b->seg_sig[k].p, kn * 16, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(in_pos + at, b->seg_pos[k].p, kn * 8, hipMemcpyHostToDevice, st));
+            at += kn;
+        }
+        HIP_OK(hipMemsetAsync(d_cnt, 0, 8, st));
+        if (tot)
+            k_range_compact<<<grid_for(c->num_cus, tot), 256, 0, st>>>(in_sig, in_pos, tot, (uint32_t)mult, (uint32_t)b_lo,
+                                                              (uint32_t)b_hi, out_sig, out_pos, d_cnt);
+        if ((r = launch_status())) return r;
+        unsigned long long got = 0;
+        HIP_OK(hipMemcpyAsync(&got, d_cnt, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        ps = GovSrc{};
+        ps.sig = tot ? (const uint64_t *)out_sig : reinterpret_cast<const uint64_t *>(16);  // (n == 0: never read)
+        ps.n = got;
+        *pos = out_pos;
+        return BSDB_OK;
+    };
+}
+
 // The build of everything added so far (caller holds the context lock).
 int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, const char *index_path,
                           const char *index_a_path, bsdb_mph **out, uint32_t *passes_used) {
@@ -918,50 +966,10 @@ int builder_finish_locked(bsdb_builder *b, uint32_t width, uint32_t passes, cons
         }
     }
     mark("records placed");
-    if (b->spill) {
-        // Spill mode: pass p's keys are those of the 256 host segments that
-        // can hold its buckets [b_lo, b_hi) -- the segment is sig0's top byte
-        // and the bucket is monotone in sig0 (CBHS:129-138, 900, 965), so a
-        // contiguous run of segments, the two at its ends shared with the
-        // neighbouring passes -- uploaded and compacted to the range on the
-        // device; each key's add position goes into its slot (positions mode).
-        const uint64_t mult = 2 * (n / BUCKET_SIZE + 1);
+    if (b->spill) {  // each pass's keys from the host segments, add positions in the slots
         sink.positions = true;
-        sink.source_bytes_per_key = 2 * 24 + 8;
-        sink.source = [&](uint64_t b_lo, uint64_t b_hi, GovSrc &ps, const uint64_t **pos) -> int {
-            auto x_first = [&](uint64_t bk) { return (((unsigned __int128)bk << 64) + mult - 1) / mult; };  // first sig0 >>> 1 of bucket bk
-            const uint32_t s_a = (uint32_t)(x_first(b_lo) >> 55), s_b = (uint32_t)((x_first(b_hi) - 1) >> 55);
-            uint64_t tot = 0;
-            for (uint32_t k = s_a; k <= s_b && k < NSEG; ++k) tot += b->seg_sig[k].n;
-            int r;
-            if ((r = sp_in.grow(tot * 24 + 256)) || (r = sp_out.grow(tot * 24 + 512)))
-                return r;
-            ulonglong2 *in_sig = sp_in.as<ulonglong2>(), *out_sig = sp_out.as<ulonglong2>();
-            uint64_t *in_pos = (uint64_t *)(in_sig + tot), *out_pos = (uint64_t *)(out_sig + tot);
-            unsigned long long *d_cnt = (unsigned long long *)(out_pos + tot);
-            hipStream_t st = c->stream;
-            uint64_t at = 0;
-            for (uint32_t k = s_a; k <= s_b && k < NSEG; ++k) {
-                const uint64_t kn = b->seg_sig[k].n;
-                if (!kn) continue;
-                HIP_OK(hipMemcpyAsync(in_sig + at, b->seg_sig[k].p, kn * 16, hipMemcpyHostToDevice, st));
-                HIP_OK(hipMemcpyAsync(in_pos + at, b->seg_pos[k].p, kn * 8, hipMemcpyHostToDevice, st));
-                at += kn;
-            }
-            HIP_OK(hipMemsetAsync(d_cnt, 0, 8, st));
-            if (tot)
-                k_range_compact<<<grid_for(c->num_cus, tot), 256, 0, st>>>(in_sig, in_pos, tot, (uint32_t)mult, (uint32_t)b_lo,
-                                                                  (uint32_t)b_hi, out_sig, out_pos, d_cnt);
-            if ((r = launch_status())) return r;
-            unsigned long long got = 0;
-            HIP_OK(hipMemcpyAsync(&got, d_cnt, 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            ps = GovSrc{};
-            ps.sig = tot ? (const uint64_t *)out_sig : reinterpret_cast<const uint64_t *>(16);  // (n == 0: never read)
-            ps.n = got;
-            *pos = out_pos;
-            return BSDB_OK;
-        };
+        sink.source_bytes_per_key = SPILL_SOURCE_BYTES_PER_KEY;
+        sink.source = spill_source(b, sp_in, sp_out);
     }
     rc = passes_build(c, src, n, width, passes, dev_addr, b->addr_base, b->addr_stride, p->E, p->values, p->sigbits,
                       sink, passes_used, c->stream);

@@ -105,6 +105,9 @@ struct GovBuild {
     GovSolvePlan sp;      // (from gov_group on)
     uint64_t n_local = 0;
     uint64_t *pay = nullptr;
+    // the grouping alone, with positions (the duplicate finder, capi_dup.hip):
+    // no solver scratch is reserved
+    bool group_only = false;
     uint64_t *Eb() const { return d_E + b_lo; }
     uint64_t *sorted() const { return c->g_sorted.as<uint64_t>(); }
     uint32_t *status() const { return c->g_status.as<uint32_t>(); }
@@ -179,13 +182,13 @@ static int gov_group(GovBuild &b) {
     if (b.n_found) *b.n_found = n_local;
     if (e_lo + n_local > b.n_global) return BSDB_EINVAL;
     if (b.ixo.slots && !(b.ixo.index = b.ixo.slots(n_local))) return BSDB_ENOMEM;
-    const GovSolvePlan &sp = b.sp = gov_solve_plan(g, n_local, b.d_rank || b.ixo.index, b.width, b.knobs, gov_sizes());
+    const GovSolvePlan &sp = b.sp = gov_solve_plan(g, n_local, b.d_rank || b.ixo.index || b.group_only, b.width, b.knobs, gov_sizes());
     if ((rc = c->g_sorted.grow(sp.sorted_bytes))) return rc;
     if (sp.need_pay) {
         if ((rc = c->g_pay.grow(sp.pay_bytes))) return rc;
         b.pay = c->g_pay.as<uint64_t>();
     }
-    if ((rc = c->g_big.grow(sp.big_bytes)) || (rc = c->g_scratch.grow(sp.scratch_bytes))) return rc;
+    if ((rc = c->g_big.grow(sp.big_bytes)) || (!b.group_only && (rc = c->g_scratch.grow(sp.scratch_bytes)))) return rc;
     uint64_t *sorted = b.sorted(), *pay = b.pay;
     unsigned long long *cursor = c->g_cursor.as<unsigned long long>();
     k_cursor_init<<<sp.cursor_grid, 256, 0, s>>>(Eb, nb, e_lo, c->g_cursor.as<uint64_t>());

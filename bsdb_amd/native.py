@@ -129,6 +129,15 @@ SIGNATURES = [
     ("bsdb_mph_verify_index_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
     ("bsdb_mph_verify_index_var", _i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
     ("bsdb_kv_verify_index", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, _i, C.c_char_p, C.c_char_p, _u32, _vp]),
+    ("bsdb_dev_find_duplicates_fixed", _i, [_vp, _vp, _u32, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_find_duplicates_var", _i, [_vp, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_find_duplicates_sig", _i, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    ("bsdb_dev_classify_pairs_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp]),
+    ("bsdb_dev_classify_pairs_var", _i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    ("bsdb_find_duplicates_fixed", _i, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp]),
+    ("bsdb_find_duplicates_var", _i, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    ("bsdb_builder_find_duplicates", _i, [_vp, _u64, _vp, _vp, _vp]),
+    ("bsdb_kv_find_duplicates", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, _u64, _vp, _vp, _vp]),
 ]
 
 BSDB_EVERIFY = -74
@@ -137,6 +146,14 @@ VERIFY_WORDS = 8
 VERIFY_FIELDS = ("records", "rejected", "in_window", "wrong_addr", "wrong_value", "min_bad_addr", "flags", "windows")
 VERIFY_E_INVALID, VERIFY_INDEX_SIZE, VERIFY_RECORD_COUNT = 1, 2, 4  # bits of "flags"
 
+BSDB_EDUP = -17
+DUP_WORDS = 4
+# the report's words in the header's order (uint64_t[BSDB_DUP_WORDS])
+DUP_FIELDS = ("found", "collisions", "flags", "keys")
+DUP_LIST_FULL, DUP_PARTIAL = 1, 2  # bits of "flags"
+DUP_SAME_KEY, DUP_COLLISION, DUP_UNCOMPARED = 0, 1, 2  # a pair's kind
+DUP_DEFAULT_CAP = 1 << 16
+
 HIST_AUTO, HIST_PARTITIONED, HIST_ATOMIC = 0, 1, 2
 
 
@@ -144,6 +161,36 @@ class BsdbError(RuntimeError):
     def __init__(self, fn: str, code: int):
         super().__init__(f"{fn} failed: {code} ({ERRORS.get(code, '?')})")
         self.code = code
+
+
+class DuplicateKeyError(BsdbError):
+    """A build that ended with BSDB_EDUP, with what the duplicate finder found:
+    ``report`` is the finder's dict (``pairs``, ``kinds``, ``found``, ...),
+    ``keys`` the first <= 16 duplicate keys as bytes.  ``code`` stays -17, so
+    code that catches BsdbError and checks it keeps working."""
+
+    def __init__(self, fn: str, report: dict, keys=()):
+        super().__init__(fn, BSDB_EDUP)
+        self.report = report
+        self.keys = list(keys)
+        shown = ", ".join(repr(k) for k in self.keys[:4])
+        self.args = (f"{self.args[0]}: {report['found']} duplicate pair(s)"
+                     + (f", {report['collisions']} of them signature collisions" if report.get("collisions") else "")
+                     + (f"; keys {shown}" + (" ..." if len(self.keys) > 4 else "") if self.keys else ""),)
+
+
+def _dup_report(pairs, kinds, report) -> dict:
+    """The finder's result as a dict: the listed pairs sorted (rows by anchor,
+    then other), their kinds in the same order, and the report's words."""
+    import numpy as np
+    found, collisions, flags, keys = (int(x) for x in report)
+    k = min(found, pairs.shape[0])
+    pairs = np.asarray(pairs[:k], np.uint64).reshape(k, 2)
+    order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+    rep = {"pairs": pairs[order], "kinds": np.asarray(kinds[:k], np.uint8)[order] if kinds is not None else None,
+           "found": found, "collisions": collisions, "list_full": bool(flags & DUP_LIST_FULL),
+           "partial": bool(flags & DUP_PARTIAL), "keys": keys}
+    return rep
 
 
 _lib: Optional[C.CDLL] = None
@@ -662,6 +709,108 @@ class Context:
             *self._verify_args(n, E, values, width, sigbits, start, length, index, index_a, out, stream)))
         return self._verify_counters(out)
 
+    # ---- which keys are duplicates (the query behind BSDB_EDUP)
+    @staticmethod
+    def _dup_bufs(device, cap: int, kinds: bool = True):
+        import torch
+        pairs = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=device)
+        kd = torch.zeros(max(cap, 1), dtype=torch.uint8, device=device) if kinds else None
+        report = torch.zeros(DUP_WORDS, dtype=torch.int64, device=device)
+        return pairs, kd, report
+
+    @staticmethod
+    def _dup_result(cap: int, pairs, kinds, report) -> dict:
+        import numpy as np
+        rep = [int(x) & (2**64 - 1) for x in report.cpu().tolist()]
+        k = min(rep[0], cap)
+        return _dup_report(pairs[:k].cpu().numpy().view(np.uint64), kinds[:k].cpu().numpy() if kinds is not None else None,
+                           rep)
+
+    def find_duplicates_fixed(self, keys, key_len: int, n: Optional[int] = None, passes: int = 0,
+                              cap: int = DUP_DEFAULT_CAP, stream=None) -> dict:
+        """bsdb_dev_find_duplicates_fixed over keys resident on the device:
+        {"pairs": ndarray[k, 2] of input positions, sorted, "kinds", "found",
+        "collisions", "list_full", "partial", "keys"}."""
+        if n is None:
+            n = keys.numel() // key_len
+        pairs, kinds, report = self._dup_bufs(keys.device, cap)
+        _check("bsdb_dev_find_duplicates_fixed", lib().bsdb_dev_find_duplicates_fixed(
+            self._h, _ptr(keys), key_len, n, passes, cap, _ptr(pairs), _ptr(kinds), _ptr(report), _stream(stream)))
+        return self._dup_result(cap, pairs, kinds, report)
+
+    def find_duplicates_var(self, blob, offsets, passes: int = 0, cap: int = DUP_DEFAULT_CAP, stream=None) -> dict:
+        """bsdb_dev_find_duplicates_var: a key blob with int64 offsets[n + 1] on the device."""
+        n = offsets.numel() - 1
+        pairs, kinds, report = self._dup_bufs(offsets.device, cap)
+        _check("bsdb_dev_find_duplicates_var", lib().bsdb_dev_find_duplicates_var(
+            self._h, _ptr(blob), blob.numel(), _ptr(offsets), n, passes, cap, _ptr(pairs), _ptr(kinds), _ptr(report),
+            _stream(stream)))
+        return self._dup_result(cap, pairs, kinds, report)
+
+    def find_duplicates_sig(self, sig, cap: int = DUP_DEFAULT_CAP, stream=None) -> dict:
+        """bsdb_dev_find_duplicates_sig: (n, 2) int64 signatures on the device; positions, no kinds."""
+        n = sig.shape[0]
+        pairs, _, report = self._dup_bufs(sig.device, cap, kinds=False)
+        _check("bsdb_dev_find_duplicates_sig", lib().bsdb_dev_find_duplicates_sig(
+            self._h, _ptr(sig) if n else None, n, cap, _ptr(pairs), _ptr(report), _stream(stream)))
+        return self._dup_result(cap, pairs, None, report)
+
+    def classify_pairs_fixed(self, keys, key_len: int, pairs, n: Optional[int] = None, stream=None):
+        """bsdb_dev_classify_pairs_fixed: the kind (0 same key, 1 collision) of
+        each row of `pairs` (int64 [k, 2] positions, device); a uint8 tensor."""
+        import torch
+        if n is None:
+            n = keys.numel() // key_len
+        k = pairs.shape[0]
+        kinds = torch.zeros(max(k, 1), dtype=torch.uint8, device=keys.device)
+        _check("bsdb_dev_classify_pairs_fixed", lib().bsdb_dev_classify_pairs_fixed(
+            self._h, _ptr(keys), key_len, n, _ptr(pairs), k, _ptr(kinds), _stream(stream)))
+        return kinds[:k]
+
+    def classify_pairs_var(self, blob, offsets, pairs, stream=None):
+        """bsdb_dev_classify_pairs_var: as classify_pairs_fixed for a blob with offsets."""
+        import torch
+        k = pairs.shape[0]
+        kinds = torch.zeros(max(k, 1), dtype=torch.uint8, device=offsets.device)
+        _check("bsdb_dev_classify_pairs_var", lib().bsdb_dev_classify_pairs_var(
+            self._h, _ptr(blob), blob.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(pairs), k, _ptr(kinds),
+            _stream(stream)))
+        return kinds[:k]
+
+    @staticmethod
+    def _dup_host_bufs(cap: int):
+        import numpy as np
+        return np.zeros((max(cap, 1), 2), np.uint64), np.zeros(max(cap, 1), np.uint8), np.zeros(DUP_WORDS, np.uint64)
+
+    def find_duplicates_fixed_host(self, keys_np, key_len: int, cap: int = DUP_DEFAULT_CAP) -> dict:
+        """bsdb_find_duplicates_fixed: keys in host memory, streamed through a builder."""
+        import numpy as np
+        keys_np = np.ascontiguousarray(keys_np, np.uint8)
+        pairs, kinds, report = self._dup_host_bufs(cap)
+        _check("bsdb_find_duplicates_fixed", lib().bsdb_find_duplicates_fixed(
+            self._h, keys_np.ctypes.data, key_len, keys_np.size // key_len, cap, pairs.ctypes.data, kinds.ctypes.data,
+            report.ctypes.data))
+        return _dup_report(pairs[:cap], kinds[:cap], report)
+
+    def find_duplicates_var_host(self, blob_np, off_np, cap: int = DUP_DEFAULT_CAP) -> dict:
+        """bsdb_find_duplicates_var: a key blob with offsets in host memory."""
+        blob_np, off_np, n = self._var_host_args(blob_np, off_np)
+        pairs, kinds, report = self._dup_host_bufs(cap)
+        _check("bsdb_find_duplicates_var", lib().bsdb_find_duplicates_var(
+            self._h, blob_np.ctypes.data, off_np.ctypes.data, n, cap, pairs.ctypes.data, kinds.ctypes.data,
+            report.ctypes.data))
+        return _dup_report(pairs[:cap], kinds[:cap], report)
+
+    def kv_find_duplicates(self, kv_base: str, partitions: int, fmt: int = 0, block_size: int = 4096, threads: int = 0,
+                           cap: int = DUP_DEFAULT_CAP) -> dict:
+        """bsdb_kv_find_duplicates: the duplicate records of kv.db files, as
+        pairs of record addresses (kv_scan's "addr")."""
+        pairs, kinds, report = self._dup_host_bufs(cap)
+        _check("bsdb_kv_find_duplicates", lib().bsdb_kv_find_duplicates(
+            self._h, kv_base.encode(), partitions, fmt, block_size, threads, cap, pairs.ctypes.data, kinds.ctypes.data,
+            report.ctypes.data))
+        return _dup_report(pairs[:cap], kinds[:cap], report)
+
     def gen_keys_var(self, first: int, n: int, stream=None):
         """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1])."""
         import torch
@@ -905,6 +1054,14 @@ class Builder:
             self._h, width, passes, index_path.encode() if index_path else None,
             index_a_path.encode() if index_a_path else None, C.byref(h), C.byref(used)))
         return Mph(h, self.ctx), used.value
+
+    def find_duplicates(self, cap: int = DUP_DEFAULT_CAP) -> dict:
+        """bsdb_builder_find_duplicates: the duplicates among everything added
+        so far, as pairs of record ADDRESSES (valid before finish)."""
+        pairs, kinds, report = Context._dup_host_bufs(cap)
+        _check("bsdb_builder_find_duplicates", lib().bsdb_builder_find_duplicates(
+            self._h, cap, pairs.ctypes.data, kinds.ctypes.data, report.ctypes.data))
+        return _dup_report(pairs[:cap], kinds[:cap], report)
 
 
 class IndexWriter:

@@ -40,7 +40,7 @@ from typing import Optional
 import numpy as np
 
 from . import kvfiles
-from .native import Context, Mph
+from .native import BSDB_EDUP, BsdbError, Context, DuplicateKeyError, Mph
 
 SLOT_SIZE = 8          # Common.java SLOT_SIZE
 MAX_KEY_SIZE = 255     # Common.java MAX_KEY_SIZE
@@ -137,8 +137,16 @@ class BSDBWriter:
     # W:91-97
     def build(self, verify: bool = False):
         """verify=True: the finished files are checked on the device
-        (``verify``) and a database that is not clean raises."""
-        mph = self._build()
+        (``verify``) and a database that is not clean raises.  A build that
+        ends with BSDB_EDUP ("keys must not have duplicates", CBHS:969-972)
+        raises DuplicateKeyError: a BsdbError with code -17 that also says
+        which records collide (``.report``, ``.keys``)."""
+        try:
+            mph = self._build()
+        except BsdbError as e:
+            if e.code != BSDB_EDUP or isinstance(e, DuplicateKeyError):
+                raise
+            raise self._duplicate_error() from e
         if verify:
             self.verify(mph)
         return mph
@@ -154,6 +162,31 @@ class BSDBWriter:
         if not rep["ok"]:
             raise VerifyError(rep)
         return rep
+
+    def _duplicate_error(self) -> DuplicateKeyError:
+        """The duplicate finder over what the failed build read: the records
+        held here (pairs of input positions), or with from_files the kv.db
+        files (bsdb_kv_find_duplicates: pairs of record addresses, mapped back
+        through the addresses the kv.db writer returned)."""
+        if self.from_files:
+            fn = "bsdb_kv_build_index"
+            rep = self.ctx.kv_find_duplicates(os.path.join(self.base, "kv.db"), self.partitions)
+            order = np.argsort(self._addr, kind="stable")
+            at = np.searchsorted(self._addr, rep["pairs"].reshape(-1), sorter=order)
+            positions = order[np.minimum(at, max(order.size - 1, 0))] if order.size else at
+        else:
+            fn = "bsdb_mph_build_var"
+            rep = self.ctx.find_duplicates_var_host(self._blob, self._off)
+            positions = rep["pairs"].reshape(-1)
+        keys, seen = [], set()
+        for p in positions.tolist():
+            k = self._blob[int(self._off[p]): int(self._off[p + 1])].tobytes()
+            if k not in seen:
+                seen.add(k)
+                keys.append(k)
+                if len(keys) == 16:
+                    break
+        return DuplicateKeyError(fn, rep, keys)
 
     def _build(self):
         blob, off, vals = self._records()

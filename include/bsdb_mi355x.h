@@ -605,6 +605,94 @@ int bsdb_kv_verify_index(bsdb_mph *mph, const char *kv_base, int partitions, int
                          int threads, int approximate, const char *index_path, const char *index_a_path,
                          uint32_t windows, uint64_t *out);
 
+/* ---------------------------------------------------------------------------
+ * Which keys are duplicates: the query behind BSDB_EDUP.  "Keys must not have
+ * duplicates" is the reference's one hard input rule (CBHS:969-972,
+ * GOV:471-479); a build that meets two equal 128-bit signatures returns
+ * BSDB_EDUP and no more.  These calls run the build's grouping again (hash,
+ * bucket, sort with each key's input position, by bucket-range passes; no
+ * solve) and list the colliding records.  They change nothing in the build:
+ * BSDB_EDUP is returned where it always was.
+ *
+ * Groups and pairs.  A group is a maximal set of input keys with equal
+ * (sig0, sig1) at seed 0, as the build hashes them.  A group of r keys is
+ * reported as r - 1 pairs (anchor, other); in the device and host forms
+ * anchor is the group's smallest input position.  The list is in no
+ * particular order.  Each pair has a kind byte:
+ *   BSDB_DUP_SAME_KEY    the two keys' bytes and lengths are equal
+ *   BSDB_DUP_COLLISION   they differ: distinct keys with one signature (the
+ *                        reference reseeds then; this build cannot)
+ *   BSDB_DUP_UNCOMPARED  the key bytes were not available (a builder in spill
+ *                        mode keeps signatures and positions only)
+ * The report is uint64_t[BSDB_DUP_WORDS]:
+ *   [0] pairs found: the total, which may exceed cap
+ *   [1] how many of the LISTED pairs are BSDB_DUP_COLLISION
+ *   [2] flags: BSDB_DUP_LIST_FULL = found > cap (the list then holds some cap
+ *       of the pairs, all valid and distinct); BSDB_DUP_PARTIAL = a bucket held
+ *       more than 16 384 keys (the sort's limit, where the build returns
+ *       BSDB_E2BIG): its keys were examined in consecutive chunks of 16 384,
+ *       so a group may be reported as one group per chunk, a key with a single
+ *       copy in each of two chunks is missed, and [0] is a lower bound --
+ *       remove what was reported and run again
+ *   [3] keys examined
+ * Finding duplicates is not an error: every form returns BSDB_OK with
+ * [0] >= 0; the usual codes report bad arguments, memory and I/O.  cap = 0
+ * (no list, d_pairs / d_kinds may be NULL) still counts.  All forms return
+ * after the device finished.  Device memory per pass: 16 + 8 B per key of the
+ * pass, plus the list (16 + 1 B per pair of cap).
+ *
+ * bsdb_dev_find_duplicates_fixed / _var: keys resident on the device, as for
+ *   bsdb_dev_mph_build_index_passes_* (d_keys / d_blob 4-byte aligned);
+ *   passes = 0 picks the fewest passes that fit the free HBM.  d_pairs[2 cap]
+ *   (u64 positions), d_kinds[cap] (may be NULL: not compared),
+ *   d_report[BSDB_DUP_WORDS].
+ * bsdb_dev_find_duplicates_sig: n signatures (sig0, sig1 interleaved, 16-byte
+ *   aligned) in one pass; positions are indices into d_sig; no kinds.  A rank
+ *   of a sharded (E4) build can call it on the signatures it owns (buckets
+ *   are those of its own n, so a narrow sig0 range only sorts larger buckets).
+ * bsdb_dev_classify_pairs_fixed / _var: d_kinds[i] = BSDB_DUP_SAME_KEY or
+ *   BSDB_DUP_COLLISION for the keys at positions d_pairs[2i], d_pairs[2i+1] of
+ *   the n keys (a position >= n gives BSDB_DUP_COLLISION).  Asynchronous.  The
+ *   key forms call it on their own list; it is exported because a signature
+ *   collision of distinct keys cannot be provoked through real hashing.
+ * bsdb_find_duplicates_fixed / _var: keys in host memory, streamed through a
+ *   builder (device memory bounded as for the build; past the device's key
+ *   area the builder spills and every kind is BSDB_DUP_UNCOMPARED).
+ * bsdb_builder_find_duplicates: everything added so far, valid before
+ *   bsdb_builder_finish (BSDB_EINVAL after it, as a second finish).  Reports
+ *   record ADDRESSES, not positions -- the caller's h_addr, or addr_base +
+ *   addr_stride * position -- which a caller that adds from several threads
+ *   can map back; which member of a group is the anchor is unspecified.
+ * bsdb_kv_find_duplicates: the kv.db scan of bsdb_kv_build_index into a
+ *   builder, then the builder form: what a caller runs after
+ *   bsdb_kv_build_index returned BSDB_EDUP.  Addresses as bsdb_kv_scan's.
+ * ------------------------------------------------------------------------- */
+#define BSDB_DUP_WORDS 4
+#define BSDB_DUP_SAME_KEY 0
+#define BSDB_DUP_COLLISION 1
+#define BSDB_DUP_UNCOMPARED 2
+#define BSDB_DUP_LIST_FULL 1
+#define BSDB_DUP_PARTIAL 2
+int bsdb_dev_find_duplicates_fixed(bsdb_ctx *ctx, const uint8_t *d_keys, uint32_t key_len, uint64_t n, uint32_t passes,
+                                   uint64_t cap, uint64_t *d_pairs, uint8_t *d_kinds, uint64_t *d_report, void *stream);
+int bsdb_dev_find_duplicates_var(bsdb_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_off,
+                                 uint64_t n, uint32_t passes, uint64_t cap, uint64_t *d_pairs, uint8_t *d_kinds,
+                                 uint64_t *d_report, void *stream);
+int bsdb_dev_find_duplicates_sig(bsdb_ctx *ctx, const uint64_t *d_sig, uint64_t n, uint64_t cap, uint64_t *d_pairs,
+                                 uint64_t *d_report, void *stream);
+int bsdb_dev_classify_pairs_fixed(bsdb_ctx *ctx, const uint8_t *d_keys, uint32_t key_len, uint64_t n,
+                                  const uint64_t *d_pairs, uint64_t count, uint8_t *d_kinds, void *stream);
+int bsdb_dev_classify_pairs_var(bsdb_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_off,
+                                uint64_t n, const uint64_t *d_pairs, uint64_t count, uint8_t *d_kinds, void *stream);
+int bsdb_find_duplicates_fixed(bsdb_ctx *ctx, const uint8_t *h_keys, uint32_t key_len, uint64_t n, uint64_t cap,
+                               uint64_t *h_pairs, uint8_t *h_kinds, uint64_t *report);
+int bsdb_find_duplicates_var(bsdb_ctx *ctx, const uint8_t *h_blob, const uint64_t *h_off, uint64_t n, uint64_t cap,
+                             uint64_t *h_pairs, uint8_t *h_kinds, uint64_t *report);
+int bsdb_builder_find_duplicates(bsdb_builder *b, uint64_t cap, uint64_t *h_addr_pairs, uint8_t *h_kinds,
+                                 uint64_t *report);
+int bsdb_kv_find_duplicates(bsdb_ctx *ctx, const char *kv_base, int partitions, int format, uint32_t block_size,
+                            int threads, uint64_t cap, uint64_t *h_addr_pairs, uint8_t *h_kinds, uint64_t *report);
+
 #ifdef __cplusplus
 }
 #endif

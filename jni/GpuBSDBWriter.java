@@ -67,6 +67,9 @@ public class GpuBSDBWriter {
     private static final boolean KEEP_FOR_VERIFY = Boolean.getBoolean("bsdb.build.verify");
     /** Words of the verification report (BSDB_VERIFY_WORDS). */
     private static final int VERIFY_WORDS = 8;
+    /** Words of the duplicate report (BSDB_DUP_WORDS) and the pairs listed in the exception. */
+    private static final int DUP_WORDS = 4;
+    private static final int DUP_LISTED = 8;
 
     private final File basePath;
     private final KVWriter kvWriter;
@@ -164,9 +167,18 @@ public class GpuBSDBWriter {
             // F3: MPHF + index.db / index_a.db from the finished data files in one call
             final PartitionedKVWriter pw = (PartitionedKVWriter) kvWriter;
             final int blockSize = nativeFormat == 1 ? ((BlockedKVWriter) kvWriter).blockSize : 0;
-            gpuMph = GpuBuild.kvBuildIndex(ctx, new File(basePath, FILE_NAME_KV_DATA).getPath(), pw.partitions,
-                    nativeFormat, blockSize, 0, checksumBits, approximateMode, indexFile().getPath(),
-                    approximateIndexFile().getPath());
+            final String kvPath = new File(basePath, FILE_NAME_KV_DATA).getPath();
+            try {
+                gpuMph = GpuBuild.kvBuildIndex(ctx, kvPath, pw.partitions, nativeFormat, blockSize, 0, checksumBits,
+                        approximateMode, indexFile().getPath(), approximateIndexFile().getPath());
+            } catch (Exception e) {
+                // BSDB_EDUP: "keys must not have duplicates" (CBHS:969-972); the reference ends such a build
+                // with an IllegalStateException (GOV:471-473, no key iterable to reseed from) -- so does this,
+                // and says which records collide
+                if (e instanceof IOException && GpuBuild.EDUP_MESSAGE.equals(e.getMessage()))
+                    throw duplicateKeys(kvPath, pw.partitions, blockSize, e);
+                throw e;
+            }
             indexWritten = true;
         } else {
             synchronized (batches) {
@@ -182,6 +194,22 @@ public class GpuBSDBWriter {
         final GOVMinimalPerfectHashFunctionModified<byte[]> f = GovAssembler.fromMph(gpuMph);
         BinIO.storeObject(f, new File(basePath, FILE_NAME_KEY_HASH));
         return f;
+    }
+
+    /** The duplicate finder over the data files (bsdb_kv_find_duplicates), as the reference's exception. */
+    private IllegalStateException duplicateKeys(String kvPath, int partitions, int blockSize, Exception cause) {
+        final long[] pairs = new long[2 * DUP_LISTED];
+        final byte[] kinds = new byte[DUP_LISTED];
+        final long[] report = new long[DUP_WORDS];
+        GpuBuild.kvFindDuplicates(ctx, kvPath, partitions, nativeFormat, blockSize, 0, pairs, kinds, report);
+        String msg = "The input contains duplicate keys: " + report[0] + " pair(s) of records"
+                + ((report[2] & 2) != 0 ? " at least" : "") + " among " + report[3] + "; record addresses";
+        final long listed = Math.min(report[0], DUP_LISTED);
+        for (int i = 0; i < listed; i++)
+            msg += " (0x" + Long.toHexString(pairs[2 * i]) + ", 0x" + Long.toHexString(pairs[2 * i + 1])
+                    + (kinds[i] == 1 ? ": distinct keys, one signature)" : ")");
+        if (report[0] > listed) msg += " ...";
+        return new IllegalStateException(msg, cause);
     }
 
     /** W:107-155 (the one-call build already wrote both files). */

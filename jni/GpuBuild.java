@@ -101,4 +101,11 @@ public final class GpuBuild {
     public static native boolean kvVerifyIndex(long mph, String kvBase, int partitions, int format, int blockSize,
                                                int threads, boolean approximate, String indexPath, String indexAPath,
                                                int windows, long[] report);
+    // After kvBuildIndex threw the IOException of BSDB_EDUP (its message is EDUP_MESSAGE): which records
+    // collide.  addrPairs receives up to addrPairs.length / 2 (anchor, other) record addresses, kinds a byte a
+    // pair (0 same key bytes, 1 a signature collision of distinct keys, 2 not compared), report[0..3] = pairs
+    // found (may exceed the list), collisions among the listed, flags (1 list full, 2 partial), keys examined
+    public static final String EDUP_MESSAGE = "duplicate key signature";
+    public static native void kvFindDuplicates(long ctx, String kvBase, int partitions, int format, int blockSize,
+                                               int threads, long[] addrPairs, byte[] kinds, long[] report);
 }

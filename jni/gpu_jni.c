@@ -15,6 +15,7 @@
  */
 #include <jni.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "bsdb_mi355x.h"
 
 #define P(x) ((void *)(intptr_t)(x))
@@ -293,4 +294,28 @@ JNIEXPORT jboolean JF(kvVerifyIndex)(JNIEnv *env, jclass c, jlong mph, jstring k
     else CHECK(rc);
     if (rc >= 0) (*env)->SetLongArrayRegion(env, report, 0, BSDB_VERIFY_WORDS, (const jlong *)out);
     return (jboolean)(rc == BSDB_OK);
+}
+/* After kvBuildIndex threw BSDB_EDUP: which records collide.  addrPairs receives up to addrPairs.length / 2
+ * (anchor, other) record addresses, kinds one byte a pair, report the BSDB_DUP_WORDS words; finding duplicates
+ * is the answer, every error code throws */
+JNIEXPORT void JF(kvFindDuplicates)(JNIEnv *env, jclass c, jlong ctx, jstring kv, jint parts, jint fmt, jint bs,
+                                    jint threads, jlongArray addrPairs, jbyteArray kinds, jlongArray report) {
+    if (!report || !addrPairs || !kinds || (*env)->GetArrayLength(env, report) < BSDB_DUP_WORDS) { fail(env, BSDB_EINVAL); return; }
+    jsize cap = (*env)->GetArrayLength(env, addrPairs) / 2;
+    if ((*env)->GetArrayLength(env, kinds) < cap) cap = (*env)->GetArrayLength(env, kinds);
+    uint64_t *pairs = malloc(cap ? (size_t)cap * 16 : 16);
+    uint8_t *kd = malloc(cap ? (size_t)cap : 1);
+    uint64_t out[BSDB_DUP_WORDS] = {0};
+    const char *k = utf(env, kv);
+    int rc = pairs && kd ? bsdb_kv_find_duplicates(P(ctx), k, parts, fmt, (uint32_t)bs, threads, (uint64_t)cap, pairs, kd, out)
+                         : BSDB_ENOMEM;
+    unutf(env, kv, k);
+    if (!rc) {
+        const jsize listed = out[0] < (uint64_t)cap ? (jsize)out[0] : cap;
+        (*env)->SetLongArrayRegion(env, addrPairs, 0, 2 * listed, (const jlong *)pairs);
+        (*env)->SetByteArrayRegion(env, kinds, 0, listed, (const jbyte *)kd);
+        (*env)->SetLongArrayRegion(env, report, 0, BSDB_DUP_WORDS, (const jlong *)out);
+    }
+    free(pairs); free(kd);
+    CHECK(rc);
 }
