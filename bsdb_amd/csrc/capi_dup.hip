@@ -192,7 +192,9 @@ int dup_dev_entry(bsdb_ctx *c, const GovSrc &src, uint64_t n, uint32_t passes, u
 
 int dup_classify_entry(bsdb_ctx *c, const GovSrc &src, const uint64_t *d_pairs, uint64_t count, uint8_t *d_kinds,
                        void *stream) {
-    if (!c || (count && (!d_pairs || !d_kinds || !src.keys)) || dup_keys_unaligned(src.keys)) return BSDB_EINVAL;
+    // (a blob with offsets at any address, as bsdb_dev_hash_var takes it: the header asks no alignment of it)
+    if (!c || (count && (!d_pairs || !d_kinds || !src.keys)) || (!src.off && dup_keys_unaligned(src.keys)))
+        return BSDB_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     HIP_OK(hipSetDevice(c->device));
     return dup_classify(c, src, d_pairs, count, d_kinds, nullptr, pick(c, stream));

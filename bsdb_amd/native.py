@@ -373,27 +373,39 @@ class Context:
         return out
 
     # ---- A5/A6/A8/A11: GOV build on the device
-    def gov_build(self, sig, width: int, stream=None):
+    @staticmethod
+    def _gov_outputs(sig, width: int, E, values, sigbits):
+        """The build's output tensors: the caller's, or fresh ones of the
+        sizes bsdb_dev_gov_build documents (sigbits None when width = 0)."""
         import torch
         n = sig.shape[0]
-        m = num_buckets(n)
-        E = torch.empty(m + 1, dtype=torch.int64, device=sig.device)
-        values = torch.empty(int(lib().bsdb_values_words(n)), dtype=torch.int64, device=sig.device)
-        sigbits = torch.empty((n * width + 63) // 64 + 1, dtype=torch.int64, device=sig.device) if width else None
+
+        def out(t, words):
+            if t is None:
+                return torch.empty(words, dtype=torch.int64, device=sig.device)
+            if t.dtype != torch.int64 or t.numel() < words or not t.is_contiguous():
+                raise ValueError("an output must be a contiguous int64 tensor of at least the documented size")
+            return t
+        return (out(E, num_buckets(n) + 1), out(values, int(lib().bsdb_values_words(n))),
+                out(sigbits, (n * width + 63) // 64 + 1) if width else None)
+
+    def gov_build(self, sig, width: int, stream=None, E=None, values=None, sigbits=None):
+        n = sig.shape[0]
+        E, values, sigbits = self._gov_outputs(sig, width, E, values, sigbits)
         _check("bsdb_dev_gov_build", lib().bsdb_dev_gov_build(
             self._h, _ptr(sig), n, width, _ptr(E), _ptr(values), _ptr(sigbits) if sigbits is not None else None,
             _stream(stream)))
         return E, values, sigbits
 
-    def gov_build_ranks(self, sig, width: int, stream=None):
+    def gov_build_ranks(self, sig, width: int, stream=None, E=None, values=None, sigbits=None, rank=None):
         """F2: (E, values, sigbits, rank) -- rank[i] = getLong of sig[i], from the solve."""
         import torch
         n = sig.shape[0]
-        m = num_buckets(n)
-        E = torch.empty(m + 1, dtype=torch.int64, device=sig.device)
-        values = torch.empty(int(lib().bsdb_values_words(n)), dtype=torch.int64, device=sig.device)
-        sigbits = torch.empty((n * width + 63) // 64 + 1, dtype=torch.int64, device=sig.device) if width else None
-        rank = torch.empty(max(n, 1), dtype=torch.int64, device=sig.device)[:n]
+        E, values, sigbits = self._gov_outputs(sig, width, E, values, sigbits)
+        if rank is None:
+            rank = torch.empty(max(n, 1), dtype=torch.int64, device=sig.device)[:n]
+        elif rank.dtype != torch.int64 or rank.numel() < n:
+            raise ValueError("rank holds fewer than n int64")
         _check("bsdb_dev_gov_build_ranks", lib().bsdb_dev_gov_build_ranks(
             self._h, _ptr(sig), n, width, _ptr(E), _ptr(values), _ptr(sigbits) if sigbits is not None else None,
             _ptr(rank), _stream(stream)))
@@ -455,14 +467,23 @@ class Context:
                 _ptr(E), _ptr(values), sb, d_index, h_index, C.byref(used), _stream(stream)))
         return E, values, sigbits, used.value
 
-    def partition_owners(self, sig, m: int, nranks: int, payload=None, stream=None):
+    def partition_owners(self, sig, m: int, nranks: int, payload=None, stream=None, out=None, payload_out=None):
         """Signatures (and one int64 payload per key) grouped by owning rank
         (bucket ranges); returns (sig_out, payload_out or None, counts)."""
         import torch
         import numpy as np
         n = sig.shape[0]
-        out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=sig.device)[:n]
-        pout = torch.empty(max(n, 1), dtype=torch.int64, device=sig.device)[:n] if payload is not None else None
+        if out is None:
+            out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=sig.device)[:n]
+        elif out.dtype != torch.int64 or out.numel() < 2 * n:
+            raise ValueError("out holds fewer than 2n int64")
+        pout = payload_out
+        if payload is None:
+            pout = None
+        elif pout is None:
+            pout = torch.empty(max(n, 1), dtype=torch.int64, device=sig.device)[:n]
+        elif pout.dtype != torch.int64 or pout.numel() < n:
+            raise ValueError("payload_out holds fewer than n int64")
         counts = np.zeros(nranks, np.uint64)
         _check("bsdb_dev_partition_owners", lib().bsdb_dev_partition_owners(
             self._h, _ptr(sig), _ptr(payload) if payload is not None else None, n, m, nranks, _ptr(out),
@@ -711,11 +732,24 @@ class Context:
 
     # ---- which keys are duplicates (the query behind BSDB_EDUP)
     @staticmethod
-    def _dup_bufs(device, cap: int, kinds: bool = True):
+    def _dup_bufs(device, cap: int, kinds: bool = True, pairs=None, kd=None, report=None):
+        """The finder's outputs: the caller's (pairs int64 [cap, 2], kinds uint8
+        [cap], report int64 [DUP_WORDS]), or zeroed ones."""
         import torch
-        pairs = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=device)
-        kd = torch.zeros(max(cap, 1), dtype=torch.uint8, device=device) if kinds else None
-        report = torch.zeros(DUP_WORDS, dtype=torch.int64, device=device)
+        if pairs is None:
+            pairs = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=device)
+        elif pairs.dtype != torch.int64 or pairs.numel() < 2 * cap:
+            raise ValueError("pairs holds fewer than 2 * cap int64")
+        if not kinds:
+            kd = None
+        elif kd is None:
+            kd = torch.zeros(max(cap, 1), dtype=torch.uint8, device=device)
+        elif kd.dtype != torch.uint8 or kd.numel() < cap:
+            raise ValueError("kinds holds fewer than cap bytes")
+        if report is None:
+            report = torch.zeros(DUP_WORDS, dtype=torch.int64, device=device)
+        elif report.dtype != torch.int64 or report.numel() < DUP_WORDS:
+            raise ValueError("report holds fewer than DUP_WORDS int64")
         return pairs, kd, report
 
     @staticmethod
@@ -727,21 +761,22 @@ class Context:
                            rep)
 
     def find_duplicates_fixed(self, keys, key_len: int, n: Optional[int] = None, passes: int = 0,
-                              cap: int = DUP_DEFAULT_CAP, stream=None) -> dict:
+                              cap: int = DUP_DEFAULT_CAP, stream=None, pairs=None, kinds=None, report=None) -> dict:
         """bsdb_dev_find_duplicates_fixed over keys resident on the device:
         {"pairs": ndarray[k, 2] of input positions, sorted, "kinds", "found",
         "collisions", "list_full", "partial", "keys"}."""
         if n is None:
             n = keys.numel() // key_len
-        pairs, kinds, report = self._dup_bufs(keys.device, cap)
+        pairs, kinds, report = self._dup_bufs(keys.device, cap, True, pairs, kinds, report)
         _check("bsdb_dev_find_duplicates_fixed", lib().bsdb_dev_find_duplicates_fixed(
             self._h, _ptr(keys), key_len, n, passes, cap, _ptr(pairs), _ptr(kinds), _ptr(report), _stream(stream)))
         return self._dup_result(cap, pairs, kinds, report)
 
-    def find_duplicates_var(self, blob, offsets, passes: int = 0, cap: int = DUP_DEFAULT_CAP, stream=None) -> dict:
+    def find_duplicates_var(self, blob, offsets, passes: int = 0, cap: int = DUP_DEFAULT_CAP, stream=None,
+                            pairs=None, kinds=None, report=None) -> dict:
         """bsdb_dev_find_duplicates_var: a key blob with int64 offsets[n + 1] on the device."""
         n = offsets.numel() - 1
-        pairs, kinds, report = self._dup_bufs(offsets.device, cap)
+        pairs, kinds, report = self._dup_bufs(offsets.device, cap, True, pairs, kinds, report)
         _check("bsdb_dev_find_duplicates_var", lib().bsdb_dev_find_duplicates_var(
             self._h, _ptr(blob), blob.numel(), _ptr(offsets), n, passes, cap, _ptr(pairs), _ptr(kinds), _ptr(report),
             _stream(stream)))
@@ -755,23 +790,30 @@ class Context:
             self._h, _ptr(sig) if n else None, n, cap, _ptr(pairs), _ptr(report), _stream(stream)))
         return self._dup_result(cap, pairs, None, report)
 
-    def classify_pairs_fixed(self, keys, key_len: int, pairs, n: Optional[int] = None, stream=None):
+    @staticmethod
+    def _kinds_out(kinds, k: int, device):
+        import torch
+        if kinds is None:
+            return torch.zeros(max(k, 1), dtype=torch.uint8, device=device)
+        if kinds.dtype != torch.uint8 or kinds.numel() < k:
+            raise ValueError("kinds holds fewer bytes than there are pairs")
+        return kinds
+
+    def classify_pairs_fixed(self, keys, key_len: int, pairs, n: Optional[int] = None, stream=None, kinds=None):
         """bsdb_dev_classify_pairs_fixed: the kind (0 same key, 1 collision) of
         each row of `pairs` (int64 [k, 2] positions, device); a uint8 tensor."""
-        import torch
         if n is None:
             n = keys.numel() // key_len
         k = pairs.shape[0]
-        kinds = torch.zeros(max(k, 1), dtype=torch.uint8, device=keys.device)
+        kinds = self._kinds_out(kinds, k, keys.device)
         _check("bsdb_dev_classify_pairs_fixed", lib().bsdb_dev_classify_pairs_fixed(
             self._h, _ptr(keys), key_len, n, _ptr(pairs), k, _ptr(kinds), _stream(stream)))
         return kinds[:k]
 
-    def classify_pairs_var(self, blob, offsets, pairs, stream=None):
+    def classify_pairs_var(self, blob, offsets, pairs, stream=None, kinds=None):
         """bsdb_dev_classify_pairs_var: as classify_pairs_fixed for a blob with offsets."""
-        import torch
         k = pairs.shape[0]
-        kinds = torch.zeros(max(k, 1), dtype=torch.uint8, device=offsets.device)
+        kinds = self._kinds_out(kinds, k, offsets.device)
         _check("bsdb_dev_classify_pairs_var", lib().bsdb_dev_classify_pairs_var(
             self._h, _ptr(blob), blob.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(pairs), k, _ptr(kinds),
             _stream(stream)))
@@ -811,16 +853,23 @@ class Context:
             report.ctypes.data))
         return _dup_report(pairs[:cap], kinds[:cap], report)
 
-    def gen_keys_var(self, first: int, n: int, stream=None):
-        """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1])."""
+    def gen_keys_var(self, first: int, n: int, stream=None, offsets=None, blob=None):
+        """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1]).
+        offsets / blob: the caller's tensors (blob.numel() is the capacity the
+        library checks the key bytes against)."""
         import torch
-        off = torch.empty(n + 1, dtype=torch.int64, device=f"cuda:{self.device}")
+        off = offsets
+        if off is None:
+            off = torch.empty(n + 1, dtype=torch.int64, device=f"cuda:{self.device}")
+        elif off.dtype != torch.int64 or off.numel() < n + 1:
+            raise ValueError("offsets holds fewer than n + 1 int64")
         _check("bsdb_dev_gen_keys_var", lib().bsdb_dev_gen_keys_var(self._h, first, n, _ptr(off), None, 0,
                                                                     _stream(stream)))
-        total = int(off[-1])
-        blob = torch.empty(total + 16, dtype=torch.uint8, device=f"cuda:{self.device}")
+        if blob is None:
+            total = int(off[n])
+            blob = torch.empty(total + 16, dtype=torch.uint8, device=f"cuda:{self.device}")
         _check("bsdb_dev_gen_keys_var", lib().bsdb_dev_gen_keys_var(self._h, first, n, _ptr(off), _ptr(blob),
-                                                                    total + 16, _stream(stream)))
+                                                                    blob.numel(), _stream(stream)))
         return blob, off
 
     def gen_keys13(self, first: int, n: int, out=None, stream=None):

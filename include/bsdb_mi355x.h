@@ -78,6 +78,8 @@ uint64_t bsdb_num_buckets(uint64_t n);
  * A3: per-key SpookyHash-short signature (sig0, sig1) = Hashes.spooky4(key, seed)
  * (CBHS:360-364 add(); in-tree C spec spooky.c:94-175).  d_sig receives 2n u64
  * (sig0, sig1 interleaved).  seed is the store seed (0 for BSDBWriter, CBHS:209).
+ * Alignment: d_keys (fixed-length keys) and d_sig must be 16-byte aligned
+ * (BSDB_EINVAL otherwise); d_blob may start at any address.
  * ------------------------------------------------------------------------- */
 int bsdb_dev_hash_fixed(bsdb_ctx *ctx, const uint8_t *d_keys, uint32_t key_len, uint64_t n,
                         uint64_t seed, uint64_t *d_sig, void *stream);
@@ -93,6 +95,8 @@ int bsdb_dev_hash_var(bsdb_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes,
  * replacement for the producer loop GOV:385-402 (edgeOffsetAndSeed[b+1] =
  * edgeOffsetAndSeed[b] + bucket.size()).  Calling it once per key shard and
  * summing d_counts across devices (RCCL all-reduce) gives the global histogram.
+ * Alignment: d_keys (fixed-length keys) must be 16-byte aligned (BSDB_EINVAL
+ * otherwise); d_blob may start at any address.
  * ------------------------------------------------------------------------- */
 int bsdb_dev_histogram_fixed(bsdb_ctx *ctx, const uint8_t *d_keys, uint32_t key_len, uint64_t n,
                              uint64_t seed, uint64_t num_buckets, uint32_t *d_counts, void *stream);
@@ -118,6 +122,8 @@ int bsdb_dev_edge_offsets(bsdb_ctx *ctx, const uint32_t *d_counts, uint64_t num_
  * A13 (W:129-145): for records whose rank lies in [start, start+len):
  * index[rank-start] = byte-reversed addr (REVERSE_ORDER, Common.java:61); with
  * d_index_a, also the first min(value_len, 8) bytes of value8 (index.approximate).
+ * Alignment: d_sig of bsdb_dev_lookup and bsdb_dev_sign must be 16-byte
+ * aligned (a signature is read as one 16-byte pair; BSDB_EINVAL otherwise).
  * ------------------------------------------------------------------------- */
 int bsdb_dev_lookup(bsdb_ctx *ctx, const uint64_t *d_sig, uint64_t nq, uint64_t n, uint64_t num_buckets,
                     const uint64_t *d_E, const uint64_t *d_values, uint32_t width,
@@ -139,6 +145,8 @@ int bsdb_dev_index_scatter(bsdb_ctx *ctx, const int64_t *d_rank, const uint64_t 
  * d_sigbits[(n*width+63)/64 + 1] (zeroed here).  The solution choice is this
  * project's deterministic solver (bit-identical to oracle/bo_gov_build), not
  * sux4j's; synchronous (returns after the device finished).
+ * Alignment: d_sig of every bsdb_dev_gov_build* call must be 16-byte aligned
+ * (BSDB_EINVAL otherwise).
  * ------------------------------------------------------------------------- */
 #define BSDB_E2BIG     (-7)   /* a bucket holds more keys than the solver supports */
 uint64_t bsdb_values_words(uint64_t n);
@@ -210,7 +218,8 @@ int bsdb_dev_mph_build_index_passes_var(bsdb_ctx *ctx, const uint8_t *d_blob, ui
  * signatures of d_sig by owning rank into d_out (rank 0's first; order within a
  * rank unspecified) together with one u64 payload per key (the record address
  * of the index stage; d_payload / d_payload_out may be NULL), and writes the
- * per-rank counts to h_counts[nranks] (synchronises). */
+ * per-rank counts to h_counts[nranks] (synchronises).  d_sig and d_out must be
+ * 16-byte aligned (BSDB_EINVAL otherwise). */
 int bsdb_dev_partition_owners(bsdb_ctx *ctx, const uint64_t *d_sig, const uint64_t *d_payload, uint64_t n,
                               uint64_t num_buckets, int nranks, uint64_t *d_out, uint64_t *d_payload_out,
                               uint64_t *h_counts, void *stream);
@@ -286,7 +295,9 @@ int bsdb_hash_var(bsdb_ctx *ctx, const uint8_t *h_blob, const uint64_t *h_off, u
                   uint64_t seed, uint64_t *h_sig);
 
 /* Synthetic SURVEY.md §8(d) D2 13-byte keys for indices [first, first+n),
- * written on device (benchmark input generator; not part of the build path). */
+ * written on device (benchmark input generator; not part of the build path).
+ * d_keys must be 16-byte aligned (BSDB_EINVAL otherwise); exactly 13 n bytes
+ * are written. */
 int bsdb_dev_gen_keys13(bsdb_ctx *ctx, uint64_t first, uint64_t n, uint8_t *d_keys, void *stream);
 
 /* Config C5 synthetic var-len keys: lengths 8..64 drawn
@@ -652,7 +663,8 @@ int bsdb_kv_verify_index(bsdb_mph *mph, const char *kv_base, int partitions, int
  *   are those of its own n, so a narrow sig0 range only sorts larger buckets).
  * bsdb_dev_classify_pairs_fixed / _var: d_kinds[i] = BSDB_DUP_SAME_KEY or
  *   BSDB_DUP_COLLISION for the keys at positions d_pairs[2i], d_pairs[2i+1] of
- *   the n keys (a position >= n gives BSDB_DUP_COLLISION).  Asynchronous.  The
+ *   the n keys (a position >= n gives BSDB_DUP_COLLISION); d_keys 4-byte
+ *   aligned, d_blob at any address.  Asynchronous.  The
  *   key forms call it on their own list; it is exported because a signature
  *   collision of distinct keys cannot be provoked through real hashing.
  * bsdb_find_duplicates_fixed / _var: keys in host memory, streamed through a
