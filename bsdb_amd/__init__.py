@@ -5,7 +5,9 @@ The package holds only what the path needs:
   native.py       ctypes binding of that C ABI (the product path; no CPU fallback)
   distributed.py  key shards, the histogram collective, the multi-GPU full build
   writer.py       host-side mirror of the reference's BSDBWriter build stages
+  reader.py       host-side mirror of the reference's SyncReader over the batched get
 """
-from .native import BsdbError, Context, IndexWriter, Mph, Multi, lib, num_buckets  # noqa: F401
+from .native import BsdbError, Context, Database, IndexWriter, Mph, Multi, lib, num_buckets  # noqa: F401
+from .reader import BSDBReader  # noqa: F401
 
-__all__ = ["BsdbError", "Context", "IndexWriter", "Mph", "Multi", "lib", "num_buckets"]
+__all__ = ["BSDBReader", "BsdbError", "Context", "Database", "IndexWriter", "Mph", "Multi", "lib", "num_buckets"]

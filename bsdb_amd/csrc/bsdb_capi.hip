@@ -7,7 +7,8 @@
 // The stages live in files included here: capi_hist.hip (histogram, with its
 // plan hist_plan.hpp), capi_gov.hip (GOV build, with its plan gov_plan.hpp),
 // capi_comm / mph / multi / passes / builder / kv / verify.hip, capi_dup.hip
-// (which keys are duplicates, with its plan dup_plan.hpp).
+// (which keys are duplicates, with its plan dup_plan.hpp), capi_get.hip
+// (batched get of a resident database, with its plan get_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -47,6 +48,7 @@
 #include "hist_plan.hpp"
 #include "gov_plan.hpp"
 #include "dup_plan.hpp"
+#include "get_kernels.hip"
 
 using namespace bsdb;
 
@@ -1035,3 +1037,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_kv.hip"
 #include "capi_verify.hip"
 #include "capi_dup.hip"
+#include "capi_get.hip"

@@ -5,11 +5,13 @@
 //   GOV = src/main/java/it/unimi/dsi/sux4j/mph/GOVMinimalPerfectHashFunctionModified.java
 
 struct bsdb_index;
+struct bsdb_db;
 
 struct bsdb_mph {
     bsdb_ctx *c = nullptr;  // nullptr once its context was closed (arrays released then)
     int device = 0;
     std::vector<bsdb_index *> ixs;  // its open index writers (detached when it is freed)
+    std::vector<bsdb_db *> dbs;     // the open databases that borrow it (capi_get.hip; detached likewise)
     uint64_t n = 0, m = 0;
     uint32_t width = 0;
     uint64_t values_words = 0, sig_words = 0;
@@ -26,7 +28,23 @@ struct bsdb_index {
     uint8_t *d_index_a = nullptr; // approximate mode: the pass's 8-byte value slots
 };
 
-// Guards the links mph -> context, mph -> index writers and index -> mph:
+// A database open for batched gets (capi_get.hip): the kv.db partitions and
+// index.db (or index_a.db alone) resident on the device.  It borrows its MPHF.
+struct bsdb_db {
+    bsdb_mph *mph = nullptr;  // nullptr once the MPHF was freed
+    int device = 0;
+    int partitions = 0, format = 0;
+    uint32_t block_size = 0;
+    bool approx = false;
+    uint64_t n = 0, batch = 0;            // slots; the host forms' chunk (0 = default)
+    uint64_t image_bytes = 0;             // exact: the partitions; approximate: index_a.db
+    uint8_t *d_image = nullptr;
+    uint64_t *d_index = nullptr;          // exact: n big-endian addresses
+    uint64_t *d_table = nullptr;          // [2][partitions]: bases, sizes
+    unsigned long long *d_report = nullptr;  // the host forms' report (and the open's structure flags)
+};
+
+// Guards the links mph -> context, mph -> index writers / databases and back:
 // bsdb_close / bsdb_mph_free may run (on a garbage collector's thread) before
 // the objects that point at them are freed; taken before a context's mph_mu.
 static std::mutex g_life_mu;
@@ -54,6 +72,8 @@ void mph_release(bsdb_mph *p) {
         }
         for (bsdb_index *ix : p->ixs) ix->mph = nullptr;  // their later calls return EINVAL
         p->ixs.clear();
+        for (bsdb_db *db : p->dbs) db->mph = nullptr;
+        p->dbs.clear();
     }
     mph_free_arrays(p);
     delete p;

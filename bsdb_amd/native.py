@@ -138,7 +138,24 @@ SIGNATURES = [
     ("bsdb_find_duplicates_var", _i, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     ("bsdb_builder_find_duplicates", _i, [_vp, _u64, _vp, _vp, _vp]),
     ("bsdb_kv_find_duplicates", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, _u64, _vp, _vp, _vp]),
+    ("bsdb_db_open", _i, [_vp, C.c_char_p, _i, _i, _u32, _i, C.c_char_p, C.POINTER(_vp)]),
+    ("bsdb_db_info", _i, [_vp, _vp]),
+    ("bsdb_db_set_batch", _i, [_vp, _u64]),
+    ("bsdb_db_get_fixed", _i, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_db_get_var", _i, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_db_free", _i, [_vp]),
+    ("bsdb_dev_db_locate_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_locate_var", _i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_gather", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp]),
 ]
+
+BSDB_E2BIG = -7
+GET_WORDS = 6
+# the get report's words in the header's order (uint64_t[BSDB_GET_WORDS])
+GET_FIELDS = ("queries", "found", "rejected", "key_mismatch", "bad_addr", "value_bytes")
+GET_FOUND, GET_REJECTED, GET_KEY_MISMATCH, GET_BAD_ADDR = 0, 1, 2, 3  # a query's status byte
+DB_INFO_WORDS = 8
+DB_INFO_FIELDS = ("n", "partitions", "format", "block_size", "approximate", "image_bytes", "index_bytes", "batch")
 
 BSDB_EVERIFY = -74
 VERIFY_WORDS = 8
@@ -853,6 +870,61 @@ class Context:
             report.ctypes.data))
         return _dup_report(pairs[:cap], kinds[:cap], report)
 
+    # ---- batched get on device-resident keys: locate -> edge_offsets(vlen) -> gather
+    @staticmethod
+    def _locate_outs(nq: int, device, src, vlen, status, report):
+        import torch
+        k = max(nq, 1)
+        if src is None:
+            src = torch.empty(k, dtype=torch.int64, device=device)
+        if vlen is None:
+            vlen = torch.empty(k, dtype=torch.int32, device=device)
+        if status is None:
+            status = torch.empty(k, dtype=torch.uint8, device=device)
+        if report is None:
+            report = torch.zeros(GET_WORDS, dtype=torch.int64, device=device)
+        if (src.dtype != torch.int64 or vlen.dtype != torch.int32 or status.dtype != torch.uint8
+                or report.dtype != torch.int64 or min(src.numel(), vlen.numel(), status.numel()) < nq
+                or report.numel() < GET_WORDS):
+            raise ValueError("src int64[nq], vlen int32[nq], status uint8[nq], report int64[GET_WORDS]")
+        return src, vlen, status, report
+
+    def db_locate_fixed(self, db: "Database", keys, key_len: int, nq: Optional[int] = None, src=None, vlen=None,
+                        status=None, report=None, stream=None):
+        """bsdb_dev_db_locate_fixed: (src, vlen, status, report) tensors of the
+        nq keys; `report` (int64[GET_WORDS], zeroed by the caller) accumulates."""
+        if nq is None:
+            nq = keys.numel() // key_len
+        src, vlen, status, report = self._locate_outs(nq, keys.device, src, vlen, status, report)
+        _check("bsdb_dev_db_locate_fixed", lib().bsdb_dev_db_locate_fixed(
+            db._h, _ptr(keys), key_len, nq, _ptr(src), _ptr(vlen), _ptr(status), _ptr(report), _stream(stream)))
+        return src[:nq], vlen[:nq], status[:nq], report
+
+    def db_locate_var(self, db: "Database", blob, offsets, src=None, vlen=None, status=None, report=None, stream=None):
+        """bsdb_dev_db_locate_var: as db_locate_fixed for a key blob with int64 offsets[nq + 1]."""
+        nq = offsets.numel() - 1
+        src, vlen, status, report = self._locate_outs(nq, offsets.device, src, vlen, status, report)
+        _check("bsdb_dev_db_locate_var", lib().bsdb_dev_db_locate_var(
+            db._h, _ptr(blob), blob.numel(), _ptr(offsets), nq, _ptr(src), _ptr(vlen), _ptr(status), _ptr(report),
+            _stream(stream)))
+        return src[:nq], vlen[:nq], status[:nq], report
+
+    def db_gather(self, db: "Database", src, voff, values=None, value_bytes: Optional[int] = None, stream=None):
+        """bsdb_dev_db_gather: value i to values[voff[i]:voff[i + 1]]; voff =
+        edge_offsets(vlen).  `values`: a uint8 tensor (any alignment) of at
+        least value_bytes = voff[nq] bytes (read back when not given)."""
+        import torch
+        nq = src.numel()
+        if value_bytes is None:
+            value_bytes = int(voff[nq])
+        if values is None:
+            values = torch.empty(max(value_bytes, 1), dtype=torch.uint8, device=src.device)
+        elif values.dtype != torch.uint8 or values.numel() < value_bytes or not values.is_contiguous():
+            raise ValueError("values holds fewer than value_bytes contiguous bytes")
+        _check("bsdb_dev_db_gather", lib().bsdb_dev_db_gather(
+            db._h, _ptr(src), _ptr(voff), nq, _ptr(values), value_bytes, _stream(stream)))
+        return values[:value_bytes]
+
     def gen_keys_var(self, first: int, n: int, stream=None, offsets=None, blob=None):
         """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1]).
         offsets / blob: the caller's tensors (blob.numel() is the capacity the
@@ -1032,12 +1104,96 @@ class Mph:
             index_path.encode(), index_a_path.encode() if index_a_path else None, windows, out)
         return _verify_report("bsdb_kv_verify_index", rc, out)
 
+    def open_db(self, kv_base: Optional[str], partitions: int, index_path: str, approximate: bool = False,
+                fmt: int = 0, block_size: int = 4096) -> "Database":
+        """bsdb_db_open: the finished database resident on this MPHF's device
+        for batched gets.  Exact mode: index_path is index.db and kv_base the
+        kv.db files' common prefix; approximate mode: index_path is index_a.db
+        (kv_base may be None)."""
+        return Database(self, kv_base, partitions, index_path, approximate, fmt, block_size)
+
     def write_index(self, index_path: str, index_a_path: Optional[str], approximate: bool, pass_cache_bytes: int,
                     feed):
         """BSDBWriter.buildIndex (W:107-155): for every pass, ``feed(put)``
         must call ``put(keys..., addr, value8, vlen)`` for every record (the
         kv.db scan).  Returns the number of passes."""
         return IndexWriter(self, index_path, index_a_path, approximate, pass_cache_bytes).run(feed)
+
+
+def _get_report(report) -> dict:
+    """The get report's words as a dict (GET_FIELDS, the header's order)."""
+    return {k: int(v) for k, v in zip(GET_FIELDS, report)}
+
+
+class Database:
+    """``bsdb_db``: a finished database resident on one device; batched gets
+    key -> value (SyncReader.getAsBytes for a batch).  Borrows its Mph."""
+
+    def __init__(self, mph: Mph, kv_base: Optional[str], partitions: int, index_path: str, approximate: bool = False,
+                 fmt: int = 0, block_size: int = 4096):
+        self.mph = mph  # keeps the MPHF (and its context) alive
+        self.approximate = approximate
+        self._h = C.c_void_p()
+        _check("bsdb_db_open", lib().bsdb_db_open(
+            mph._h, kv_base.encode() if kv_base else None, partitions, fmt, block_size, 1 if approximate else 0,
+            index_path.encode(), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _check("bsdb_db_free", lib().bsdb_db_free(self._h))
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        out = (C.c_uint64 * DB_INFO_WORDS)()
+        _check("bsdb_db_info", lib().bsdb_db_info(self._h, out))
+        return {k: int(v) for k, v in zip(DB_INFO_FIELDS, out)}
+
+    def set_batch(self, max_queries: int = 0):
+        """Queries per chunk of the host forms (0 = default); results do not depend on it."""
+        _check("bsdb_db_set_batch", lib().bsdb_db_set_batch(self._h, max_queries))
+
+    def _get(self, fn: str, call, nq: int, value_cap: Optional[int]):
+        """One host get, once more with the reported size on BSDB_E2BIG."""
+        import numpy as np
+        status = np.zeros(max(nq, 1), np.uint8)
+        voff = np.zeros(nq + 1, np.uint64)
+        report = np.zeros(GET_WORDS, np.uint64)
+        cap = (8 if self.approximate else 64) * nq if value_cap is None else value_cap
+        for _ in range(2):
+            values = np.zeros(max(cap, 1), np.uint8)
+            rc = call(cap, values.ctypes.data, voff.ctypes.data, status.ctypes.data, report.ctypes.data)
+            if rc != BSDB_E2BIG:
+                break
+            cap = int(report[5])
+        _check(fn, rc)
+        return {"status": status[:nq], "voff": voff, "values": values[: int(voff[nq])], "report": _get_report(report)}
+
+    def get_fixed(self, keys_np, key_len: int, value_cap: Optional[int] = None) -> dict:
+        """bsdb_db_get_fixed: {"status" u8[nq], "voff" u64[nq + 1], "values"
+        u8[voff[nq]], "report" dict}; value i is values[voff[i]:voff[i + 1]]."""
+        import numpy as np
+        keys_np = np.ascontiguousarray(keys_np, np.uint8)
+        nq = keys_np.size // key_len
+        return self._get("bsdb_db_get_fixed", lambda cap, v, o, s, r: lib().bsdb_db_get_fixed(
+            self._h, keys_np.ctypes.data, key_len, nq, cap, v, o, s, r), nq, value_cap)
+
+    def get_var(self, blob_np, off_np, value_cap: Optional[int] = None) -> dict:
+        """bsdb_db_get_var: as get_fixed for a key blob with offsets[nq + 1]."""
+        blob_np, off_np, nq = Context._var_host_args(blob_np, off_np)
+        return self._get("bsdb_db_get_var", lambda cap, v, o, s, r: lib().bsdb_db_get_var(
+            self._h, blob_np.ctypes.data, off_np.ctypes.data, nq, cap, v, o, s, r), nq, value_cap)
 
 
 class Builder:

@@ -36,6 +36,8 @@
  *   bsdb_index  the index.db / index_a.db writer of BSDBWriter.buildIndex
  *   bsdb_multi  one context per device of this process + an RCCL communicator
  *   bsdb_builder keys streamed into one device's HBM, built by bucket-range passes
+ *   bsdb_db     a finished database resident on one device for batched gets:
+ *               index.db and every kv.db partition in HBM; borrows its bsdb_mph
  */
 #ifndef BSDB_MI355X_H
 #define BSDB_MI355X_H
@@ -704,6 +706,99 @@ int bsdb_builder_find_duplicates(bsdb_builder *b, uint64_t cap, uint64_t *h_addr
                                  uint64_t *report);
 int bsdb_kv_find_duplicates(bsdb_ctx *ctx, const char *kv_base, int partitions, int format, uint32_t block_size,
                             int threads, uint64_t cap, uint64_t *h_addr_pairs, uint8_t *h_kinds, uint64_t *report);
+
+/* ---------------------------------------------------------------------------
+ * Batched get: a finished database read on the device, key -> value.  What
+ * SyncReader.getAsBytes does one key per call (read/SyncReader.java:44-57 ->
+ * BaseKVReader.getValueAsBytes, read/kv/BaseKVReader.java:16-31), for a batch:
+ * key -> signature -> rank (checked getLong, GOV:557-569) -> index.db slot ->
+ * address -> record -> key compare -> the value bytes, packed.
+ *
+ * bsdb_db_open makes the database resident.  format / block_size as for
+ * bsdb_kv_scan (0 compact, 1 blocked).  Exact mode (approximate = 0): index_path
+ * is index.db, loaded whole (it must be 8n bytes: BSDB_EVERIFY otherwise, as
+ * flag bit 1 of the verify report), and every <kv_base>.<p>, p < partitions
+ * <= 128 (an address is non-negative: 7 partition bits), is loaded into ONE
+ * device allocation, each partition at a 16-byte aligned base.  Approximate
+ * mode: index_path is index_a.db (8n bytes), no kv.db is read and kv_base may
+ * be NULL.  E is validated before any lookup is allowed, as the verify calls
+ * do (an imported hash.dump is untrusted: BSDB_EVERIFY when E is no valid
+ * offset array).  BSDB_ENOMEM when the files do not fit the free device
+ * memory: a host-resident or windowed kv.db is out of scope, and so are
+ * compressed kv.db files.  The db borrows the MPHF, as a bsdb_index does:
+ * after bsdb_mph_free or bsdb_close its calls return BSDB_EINVAL and
+ * bsdb_db_free only releases it (any order is safe).
+ * bsdb_db_info fills uint64_t[BSDB_DB_INFO_WORDS]: n, partitions, format,
+ * block_size, approximate, image bytes, index bytes, host chunk (queries).
+ *
+ * Every query gets a status byte, tested in this order:
+ *   BSDB_GET_REJECTED      getLong gave -1 (rank >= n, or the checksum bits differ)
+ *   BSDB_GET_BAD_ADDR      the slot's address does not denote a whole record
+ *                          inside the resident files: top bit set (SyncReader.java:
+ *                          52 returns null), partition >= partitions
+ *                          (PartitionedKVReader.java:78-82: partition = addr >>> 56,
+ *                          offset = low 56 bits), blocked layout
+ *                          (BlockedKVReader.java:42-52: block offset = ((addr >>>
+ *                          16) & 0xFFFFFFFF) * 4096, block size = ((addr >>> 48) &
+ *                          0xFF) * 4096, record offset = addr & 0xFFFF) with a
+ *                          block of size 0 or not inside its file, or the record
+ *                          [pos, pos + 3 + kLen + vLen) ([kLen u8][vLen u16 BE]
+ *                          [key][value]) not inside its file (compact) or its
+ *                          block (blocked).  index.db is untrusted: no byte
+ *                          outside the resident files is ever read.
+ *   BSDB_GET_KEY_MISMATCH  the record holds another key (kLen or bytes differ:
+ *                          the reference returns null, BaseKVReader.java:65-83)
+ *   BSDB_GET_FOUND         the value is returned
+ * A query that is not FOUND has value length 0.  Approximate mode has only
+ * FOUND and REJECTED: a found value is the 8 raw bytes of the slot
+ * (LBufferIndexReader.getRawBytesAt), no key compare, false positives included.
+ *
+ * The report is uint64_t[BSDB_GET_WORDS]:
+ *   [0] queries           [1] found
+ *   [2] rejected          [3] key_mismatch
+ *   [4] bad_addr          [5] value_bytes (the sum over found queries)
+ * bsdb_dev_db_locate_*: keys resident on the device as for bsdb_dev_verify_*
+ *   (fixed-length keys at a 4-byte aligned address).  Writes per query d_src
+ *   (the byte position of the value in the device image; approximate mode: the
+ *   slot), d_vlen (u32) and d_status, and ACCUMULATES into d_report (zeroed by
+ *   the caller, 8-byte aligned).  Asynchronous.
+ * The offsets are the u32 -> u64 exclusive scan of d_vlen, nq + 1 entries:
+ *   bsdb_dev_edge_offsets(ctx, d_vlen, nq, d_voff, stream).
+ * bsdb_dev_db_gather: value i to d_values[d_voff[i] .. d_voff[i + 1]);
+ *   value_bytes = d_voff[nq].  d_values may start at any address; nothing is
+ *   written outside [d_values, d_values + value_bytes).  Asynchronous.
+ * bsdb_db_get_*: keys in host memory (as bsdb_hash_*), streamed in chunks of
+ *   bsdb_db_set_batch queries (0 = default).  h_voff[nq + 1] is the exclusive
+ *   prefix of the value lengths over the whole call, h_voff[nq] = report[5];
+ *   value i is h_values[h_voff[i] .. h_voff[i + 1]).  When report[5] >
+ *   value_cap the call returns BSDB_E2BIG with h_voff, h_status and report
+ *   complete and h_values unspecified: the caller retries with report[5].
+ *   nq = 0 is BSDB_OK with h_voff[0] = 0.
+ * Returns: BSDB_EINVAL for bad arguments (before any device call), BSDB_EFILE
+ * for a file that cannot be read, else as above.
+ * ------------------------------------------------------------------------- */
+typedef struct bsdb_db bsdb_db;
+#define BSDB_DB_INFO_WORDS 8
+#define BSDB_GET_WORDS 6
+#define BSDB_GET_FOUND 0
+#define BSDB_GET_REJECTED 1
+#define BSDB_GET_KEY_MISMATCH 2
+#define BSDB_GET_BAD_ADDR 3
+int bsdb_db_open(bsdb_mph *mph, const char *kv_base, int partitions, int format, uint32_t block_size, int approximate,
+                 const char *index_path, bsdb_db **out);
+int bsdb_db_info(const bsdb_db *db, uint64_t *out /* BSDB_DB_INFO_WORDS */);
+int bsdb_db_set_batch(bsdb_db *db, uint64_t max_queries);
+int bsdb_db_get_fixed(bsdb_db *db, const uint8_t *h_keys, uint32_t key_len, uint64_t nq, uint64_t value_cap,
+                      uint8_t *h_values, uint64_t *h_voff, uint8_t *h_status, uint64_t *report);
+int bsdb_db_get_var(bsdb_db *db, const uint8_t *h_blob, const uint64_t *h_off, uint64_t nq, uint64_t value_cap,
+                    uint8_t *h_values, uint64_t *h_voff, uint8_t *h_status, uint64_t *report);
+int bsdb_db_free(bsdb_db *db);
+int bsdb_dev_db_locate_fixed(bsdb_db *db, const uint8_t *d_keys, uint32_t key_len, uint64_t nq, uint64_t *d_src,
+                             uint32_t *d_vlen, uint8_t *d_status, uint64_t *d_report, void *stream);
+int bsdb_dev_db_locate_var(bsdb_db *db, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_off, uint64_t nq,
+                           uint64_t *d_src, uint32_t *d_vlen, uint8_t *d_status, uint64_t *d_report, void *stream);
+int bsdb_dev_db_gather(bsdb_db *db, const uint64_t *d_src, const uint64_t *d_voff, uint64_t nq, uint8_t *d_values,
+                       uint64_t value_bytes, void *stream);
 
 #ifdef __cplusplus
 }
