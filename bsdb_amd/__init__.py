@@ -6,6 +6,7 @@ The package holds only what the path needs:
   distributed.py  key shards, the histogram collective, the multi-GPU full build
   writer.py       host-side mirror of the reference's BSDBWriter build stages
   reader.py       host-side mirror of the reference's SyncReader over the batched get
+  builder.py      the reference's Builder for text input: lines of key<sep>value -> database (build_text, CLI)
 """
 from .native import BsdbError, Context, Database, IndexWriter, Mph, Multi, lib, num_buckets  # noqa: F401
 from .reader import BSDBReader  # noqa: F401

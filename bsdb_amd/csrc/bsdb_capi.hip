@@ -8,7 +8,9 @@
 // plan hist_plan.hpp), capi_gov.hip (GOV build, with its plan gov_plan.hpp),
 // capi_comm / mph / multi / passes / builder / kv / verify.hip, capi_dup.hip
 // (which keys are duplicates, with its plan dup_plan.hpp), capi_get.hip
-// (batched get of a resident database, with its plan get_plan.hpp).
+// (batched get of a resident database, with its plan get_plan.hpp),
+// capi_text.hip (text lines into records, kv.db files and a database, with its
+// plan text_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -49,6 +51,7 @@
 #include "gov_plan.hpp"
 #include "dup_plan.hpp"
 #include "get_kernels.hip"
+#include "text_kernels.hip"
 
 using namespace bsdb;
 
@@ -169,6 +172,12 @@ struct bsdb_ctx {
     std::mutex mph_mu;
     std::vector<bsdb_mph *> mphs;
     DevBuf pack{bufs, true};
+    // text front end (capi_text.hip): per-block counts and their scans, the
+    // line-start and separator lists, the keep flags and their scan, the
+    // records' sizes and the image scan
+    DevBuf t_cnt{bufs, true}, t_off{bufs, true}, t_ls{bufs, true}, t_sp{bufs, true}, t_keep{bufs, true}, t_scan{bufs, true};
+    DevBuf t_size{bufs, true}, t_roff{bufs, true};
+    uint64_t text_chunk = 0;  // bsdb_text_set_chunk (0 = default)
     // live profiling: event pairs per launch, per kind
     bool profiling = false;
     struct Rec { hipEvent_t a, b; int kind; uint64_t keys; };
@@ -1038,3 +1047,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_verify.hip"
 #include "capi_dup.hip"
 #include "capi_get.hip"
+#include "capi_text.hip"

@@ -1,0 +1,366 @@
+// text_kernels.hip -- the text front end on gfx950: "key<sep>value" lines of
+// one chunk of text resident in HBM (< 2^32 bytes) into record descriptors,
+// and the kept records into the compact kv.db layout.  What Builder's put
+// loop does one line per call on one thread per file
+// (tools/Builder.java:144-176: BufferedReader.lines, String.split(sep), put;
+// write/kv/SimpleCompactKVWriter.java:36-42 for the record layout), as
+//   k_text_count      per 16-byte piece: which bytes start a line, which are
+//                     separators; per-workgroup counts of both
+//   k_text_positions  the same classification again, scattered into two sorted
+//                     u32 position lists (offsets: k_scan_* over the counts)
+//   k_text_records    a line per lane: its end from the next line start, its
+//                     separators by two searches in the separator list, the
+//                     verdict by arithmetic (text_verdict, text_plan.hpp);
+//                     pass 0 counts and flags, pass 1 (after the scan of the
+//                     flags) writes the kept lines' descriptors in input order
+//   k_text_sizes      a record per lane: its bytes in the image and in the blob
+//   k_text_pack       driven by the output, as k_get_gather: a thread owns an
+//                     aligned 16-byte piece of the destination, finds the
+//                     records it overlaps in the size scan, assembles the
+//                     piece in registers and stores it once
+//   k_text_outputs    a record per lane: its address and its value head
+// No lane walks a line: a 32 KB value or a 1 MB junk line costs what a
+// 20-byte line costs.  Every read of the text in the pack goes through the
+// bounded reader sel_gload64 with the chunk as its limit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "get_kernels.hip"
+#include "text_plan.hpp"
+
+namespace bsdb {
+
+// The 16-byte piece k of the text: bit j of `starts` = byte 16 k + j starts a
+// line (it is byte 0, or follows a '\n', or follows a '\r' and is no '\n'),
+// bit j of `seps` = it is the separator.  Bytes past the text are neither.
+__device__ __forceinline__ void text_classify(const uint8_t *text, uint64_t bytes, uint64_t k, uint32_t sep, uint32_t &starts,
+                                              uint32_t &seps) {
+    starts = seps = 0;
+    const uint64_t p0 = k * 16;
+    if (p0 >= bytes) return;
+    uint32_t w[4];
+    if (p0 + 16 <= bytes) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(text + p0);  // (the text is 16-byte aligned)
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    } else {
+        w[0] = w[1] = w[2] = w[3] = 0;
+        for (uint32_t j = 0; p0 + j < bytes; ++j) w[j >> 2] |= (uint32_t)text[p0 + j] << (8 * (j & 3));
+    }
+    const uint32_t nvalid = bytes - p0 < 16 ? (uint32_t)(bytes - p0) : 16;
+    uint32_t prev = p0 ? text[p0 - 1] : '\n';  // (byte 0 starts a line)
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+        const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xFF;
+        const bool valid = j < nvalid;
+        if (valid && (prev == '\n' || (prev == '\r' && b != '\n'))) starts |= 1u << j;
+        if (valid && b == sep) seps |= 1u << j;
+        prev = b;
+    }
+}
+
+// exclusive scan of one u32 per thread over a 256-thread workgroup
+__device__ __forceinline__ uint32_t text_block_scan(uint32_t v, uint32_t *wsum, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= (uint32_t)d) x += y;
+    }
+    if (lane == 63) wsum[wid] = x;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+    for (uint32_t w = 0; w < 4; ++w) {
+        const uint32_t s = wsum[w];
+        pre += w < wid ? s : 0;
+        tot += s;
+    }
+    total = tot;
+    __syncthreads();
+    return pre + x - v;
+}
+
+// Workgroup g classifies text bytes [4096 g, 4096 g + 4096).
+__global__ __launch_bounds__(256) void k_text_count(const uint8_t *text, uint64_t bytes, uint32_t sep, uint32_t *cnt_starts,
+                                                    uint32_t *cnt_seps) {
+    __shared__ uint32_t wsum[4];
+    uint32_t st, sp, tot_st, tot_sp;
+    text_classify(text, bytes, (uint64_t)blockIdx.x * 256 + threadIdx.x, sep, st, sp);
+    text_block_scan(__popc(st), wsum, tot_st);
+    text_block_scan(__popc(sp), wsum, tot_sp);
+    if (threadIdx.x == 0) {
+        cnt_starts[blockIdx.x] = tot_st;
+        cnt_seps[blockIdx.x] = tot_sp;
+    }
+}
+
+// off_*: the exclusive scans of k_text_count's counts (off[blocks] = totals);
+// ls / sp receive the positions in increasing order.
+__global__ __launch_bounds__(256) void k_text_positions(const uint8_t *text, uint64_t bytes, uint32_t sep,
+                                                        const uint64_t *off_starts, const uint64_t *off_seps, uint32_t *ls,
+                                                        uint64_t ls_cap, uint32_t *sp, uint64_t sp_cap) {
+    __shared__ uint32_t wsum[4];
+    uint32_t st, se, tot;
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    text_classify(text, bytes, k, sep, st, se);
+    uint64_t at = off_starts[blockIdx.x] + text_block_scan(__popc(st), wsum, tot);
+    for (uint32_t m = st; m; m &= m - 1, ++at)
+        if (at < ls_cap) ls[at] = (uint32_t)(k * 16) + (uint32_t)__builtin_ctz(m);
+    at = off_seps[blockIdx.x] + text_block_scan(__popc(se), wsum, tot);
+    for (uint32_t m = se; m; m &= m - 1, ++at)
+        if (at < sp_cap) sp[at] = (uint32_t)(k * 16) + (uint32_t)__builtin_ctz(m);
+}
+
+// the first index in [0, n) with list[index] >= x (n when there is none)
+__device__ __forceinline__ uint64_t text_lower_bound(const uint32_t *list, uint64_t n, uint32_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (list[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct TextSplit {
+    const uint8_t *text;
+    uint64_t bytes;            // < 2^32
+    const uint32_t *ls;        // line starts, `lines` of them
+    uint64_t lines;
+    const uint32_t *sp;        // separator positions, `seps` of them
+    uint64_t seps;
+    uint32_t *keep;            // [lines] pass 0: 1 for a kept line
+    const uint64_t *keep_off;  // [lines + 1] pass 1: the scan of keep
+    uint32_t *kpos, *klen, *vpos, *vlen;  // pass 1: the kept lines' descriptors
+    uint64_t cap;              // descriptors the caller's arrays hold
+    unsigned long long *out;   // pass 0: the report (TW_WORDS), accumulated
+};
+
+// The verdict on line j.  Its end is the next line's start (the text's end
+// for the last line) minus its terminator: "\n", "\r" or "\r\n"; only the
+// last line of a text can have none.
+__device__ __forceinline__ TextLine text_line(const TextSplit &a, uint64_t j) {
+    const uint32_t start = a.ls[j];
+    const uint32_t next = j + 1 < a.lines ? a.ls[j + 1] : (uint32_t)a.bytes;  // > start
+    const uint32_t last = a.text[next - 1];
+    uint32_t end = next;
+    if (last == '\n') end = next - 1 > start && a.text[next - 2] == '\r' ? next - 2 : next - 1;
+    else if (last == '\r') end = next - 1;
+    const uint64_t lo = text_lower_bound(a.sp, a.seps, start), hi = lo + text_lower_bound(a.sp + lo, a.seps - lo, end);
+    const uint32_t c = (uint32_t)(hi - lo);
+    return text_verdict(start, end, c, c >= 1 ? a.sp[lo] : 0, c >= 2 ? a.sp[lo + 1] : 0);
+}
+
+// A line per lane; the loop is uniform per wave so the ballots see all lanes.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_text_records(TextSplit a) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    uint64_t lines = 0, kept = 0, not_two = 0, empty_key = 0, too_large = 0;  // wave totals
+    uint64_t kbytes = 0, vbytes = 0;                                          // this lane's
+    uint32_t kmax = 0, vmax = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < a.lines; base += stride) {
+        const uint64_t j = base + lane;
+        const bool active = j < a.lines;
+        int v = -1;
+        if (active) {
+            const TextLine t = text_line(a, j);
+            v = (int)t.verdict;
+            if (EMIT) {
+                const uint64_t r = a.keep_off[j];
+                if (v == TV_KEPT && r < a.cap) {
+                    a.kpos[r] = t.kpos;
+                    a.klen[r] = t.klen;
+                    a.vpos[r] = t.vpos;
+                    a.vlen[r] = t.vlen;
+                }
+            } else {
+                a.keep[j] = v == TV_KEPT;
+                if (v == TV_KEPT) {
+                    kbytes += t.klen;
+                    vbytes += t.vlen;
+                    kmax = t.klen > kmax ? t.klen : kmax;
+                    vmax = t.vlen > vmax ? t.vlen : vmax;
+                }
+            }
+        }
+        if (!EMIT) {
+            lines += __popcll(__ballot(active));
+            kept += __popcll(__ballot(v == TV_KEPT));
+            not_two += __popcll(__ballot(v == TV_NOT_TWO_FIELDS));
+            empty_key += __popcll(__ballot(v == TV_EMPTY_KEY));
+            too_large += __popcll(__ballot(v == TV_TOO_LARGE));
+        }
+    }
+    if (EMIT) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.out + TW_CHUNKS, 1ull);
+    for (int d = 32; d; d >>= 1) {
+        kbytes += __shfl_xor(kbytes, d, 64);
+        vbytes += __shfl_xor(vbytes, d, 64);
+        const uint32_t ko = __shfl_xor(kmax, d, 64), vo = __shfl_xor(vmax, d, 64);
+        kmax = ko > kmax ? ko : kmax;
+        vmax = vo > vmax ? vo : vmax;
+    }
+    if (lane == 0) {
+        if (lines) atomicAdd(a.out + TW_LINES, (unsigned long long)lines);
+        if (kept) atomicAdd(a.out + TW_RECORDS, (unsigned long long)kept);
+        if (not_two) atomicAdd(a.out + TW_NOT_TWO_FIELDS, (unsigned long long)not_two);
+        if (empty_key) atomicAdd(a.out + TW_EMPTY_KEY, (unsigned long long)empty_key);
+        if (too_large) atomicAdd(a.out + TW_TOO_LARGE, (unsigned long long)too_large);
+        if (kbytes) atomicAdd(a.out + TW_KEY_BYTES, (unsigned long long)kbytes);
+        if (vbytes) atomicAdd(a.out + TW_VALUE_BYTES, (unsigned long long)vbytes);
+        if (kmax) atomicMax(a.out + TW_MAX_KEY_LEN, (unsigned long long)kmax);
+        if (vmax) atomicMax(a.out + TW_MAX_VALUE_LEN, (unsigned long long)vmax);
+    }
+}
+
+// The lengths the pack works with: a descriptor's, cut to what a record can
+// hold, so that the sizes, the header and the copied bytes always agree.
+__device__ __forceinline__ uint32_t text_klen(uint32_t klen) { return klen < TEXT_MAX_KEY ? klen : TEXT_MAX_KEY; }
+__device__ __forceinline__ uint32_t text_vlen(uint32_t vlen) { return vlen < TEXT_MAX_VALUE ? vlen : TEXT_MAX_VALUE; }
+
+// record r's bytes in the image (header + key + value) and in the key blob
+__global__ __launch_bounds__(256) void k_text_sizes(const uint32_t *klen, const uint32_t *vlen, uint64_t count, uint32_t *rsize,
+                                                    uint32_t *ksize) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < count; r += step) {
+        const uint32_t kl = text_klen(klen[r]);
+        rsize[r] = 3 + kl + text_vlen(vlen[r]);
+        ksize[r] = kl;
+    }
+}
+
+struct TextPack {
+    const uint8_t *text;
+    uint64_t bytes;
+    const uint32_t *kpos, *klen, *vpos, *vlen;
+    uint64_t count;       // records, >= 1
+    const uint64_t *off;  // [count + 1] the scan of the records' sizes in this destination
+    uint8_t *dst;         // out_bytes = off[count] bytes, at any alignment
+    uint64_t out_bytes;
+};
+
+// IMAGE: a record is [kLen u8][vLen u16 BE][key][value]
+// (SimpleCompactKVWriter.java:36-42); otherwise its key alone (the blob the
+// hash kernels read).  Piece k is the 16 bytes at (dst & ~15) + 16 k: output
+// bytes [16 k - mis, 16 k - mis + 16) cut to [0, out_bytes).  The search for
+// the records of a piece is k_get_gather's (get_owner): the wave's first and
+// last lanes search the whole scan, the others between those two results.
+// One 16-byte store per piece; the first and last pieces of the destination
+// byte by byte, inside the destination.
+template <bool IMAGE>
+__global__ __launch_bounds__(256) void k_text_pack(TextPack a) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t mis = (uint32_t)((uintptr_t)a.dst & 15);
+    uint8_t *const aligned = a.dst - mis;
+    const uint64_t pieces = text_pack_pieces(a.out_bytes, mis);
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t wbase = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); wbase < pieces; wbase += stride) {
+        const uint64_t k = wbase + lane;
+        const bool active = k < pieces;
+        const uint64_t klast = wbase + 63 < pieces ? wbase + 63 : pieces - 1;
+        auto first_of = [&](uint64_t kk) -> uint64_t { return kk ? kk * 16 - mis : 0; };
+        auto end_of = [&](uint64_t kk) -> uint64_t {
+            const uint64_t e = kk * 16 + 16 - mis;
+            return e < a.out_bytes ? e : a.out_bytes;
+        };
+        const uint64_t w0 = first_of(wbase), w1 = end_of(klast);
+        uint64_t qlo = 0, qhi = 0;
+        if (lane == 0) qlo = get_owner(a.off, 0, a.count - 1, w0);
+        if (lane == 63) qhi = get_owner(a.off, 0, a.count - 1, w1 - 1);
+        qlo = __shfl(qlo, 0, 64);
+        qhi = __shfl(qhi, 63, 64);
+        if (!active) continue;  // (no wave-wide operation below)
+        const uint64_t o0 = first_of(k), o1 = end_of(k);
+        const uint32_t j0 = (uint32_t)(o0 + mis - k * 16);  // the piece's first valid byte
+        uint64_t lo = 0, hi = 0;
+        // nb <= 8 bytes (the low ones of x) to piece bytes j .. j + nb - 1
+        auto put = [&](uint64_t x, uint32_t j, uint32_t nb) {
+            x &= low_bytes_mask(nb);
+            if (j < 8) {
+                lo |= x << (8 * j);
+                if (j) hi |= x >> (64 - 8 * j);
+            } else {
+                hi |= x << (8 * (j - 8));
+            }
+        };
+        uint64_t q = qlo;
+        bool searched = false;
+        for (uint64_t o = o0; o < o1;) {
+            if (!searched || a.off[q + 1] <= o) {  // past q's record: the owner of o, within the wave's range
+                q = get_owner(a.off, q < qhi && searched ? q + 1 : q, qhi, o);
+                searched = true;
+            }
+            const uint64_t rs = a.off[q], re = a.off[q + 1];
+            if (rs > o || re <= o) break;  // offsets that are no scan of sizes: the rest stays zero
+            const uint64_t run_end = re < o1 ? re : o1;
+            const uint32_t kl = text_klen(a.klen[q]), vl = text_vlen(a.vlen[q]);
+            const uint32_t hdr = IMAGE ? 3 : 0;
+            // record bytes [x0, x1) go to piece bytes from jr
+            const uint32_t x0 = (uint32_t)(o - rs), x1 = (uint32_t)(run_end - rs);
+            const uint32_t jr = j0 + (uint32_t)(o - o0);
+            if (IMAGE && x0 < 3) {
+                const uint64_t h = (uint64_t)kl | (uint64_t)(vl >> 8) << 8 | (uint64_t)(vl & 0xFF) << 16;
+                const uint32_t e = x1 < 3 ? x1 : 3;
+                put(h >> (8 * x0), jr, e - x0);
+            }
+            // the key's and the value's part of [x0, x1), 8 source bytes a step
+            for (int seg = 0; seg < (IMAGE ? 2 : 1); ++seg) {
+                const uint32_t s0 = seg ? hdr + kl : hdr, s1 = seg ? hdr + kl + vl : hdr + kl;
+                const uint64_t src = seg ? a.vpos[q] : a.kpos[q];
+                const uint32_t b = x0 > s0 ? x0 : s0, e = x1 < s1 ? x1 : s1;
+                for (uint32_t x = b; x < e; x += 8) {
+                    const uint32_t nb = e - x < 8 ? e - x : 8;
+                    const uint64_t p = src + (x - s0);
+                    put(p < a.bytes ? sel_gload64(a.text, a.bytes, p) : 0, jr + (x - x0), nb);
+                }
+            }
+            o = run_end;
+        }
+        uint8_t *dst = aligned + k * 16;
+        if (o1 - o0 == 16) {
+            *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(lo, hi);
+        } else {
+            for (uint32_t j = j0; j < j0 + (uint32_t)(o1 - o0); ++j) dst[j] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))));
+        }
+    }
+}
+
+// The runs of the partition rule (text_run_bound) and where each lands:
+// record r of run p lies at file offset file_base[p] + roff[r], file_base[p] =
+// the file's size before the chunk minus roff of the run's first record.
+struct TextRuns {
+    uint32_t partitions;
+    uint64_t bound[TEXT_MAX_PARTS + 1];
+    uint64_t file_base[TEXT_MAX_PARTS];
+};
+
+// A record per lane: addr = p << 56 | offset (SimpleCompactKVWriter.java:62-73,
+// PartitionedKVWriter.java:82-96) and, for index.approximate, the value head:
+// the first min(vlen, 8) value bytes, the rest 0, and that length
+// (BSDBWriter.java:140-142).
+__global__ __launch_bounds__(256) void k_text_outputs(TextRuns runs, const uint8_t *text, uint64_t bytes, const uint32_t *vpos,
+                                                      const uint32_t *vlen, const uint64_t *roff, uint64_t count,
+                                                      uint64_t *addr, uint64_t *value8, uint8_t *value_len) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < count; r += step) {
+        if (addr) {
+            uint32_t lo = 0, hi = runs.partitions - 1;  // the last p with bound[p] <= r (empty runs share their bound)
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo + 1) / 2;
+                if (runs.bound[mid] <= r) lo = mid;
+                else hi = mid - 1;
+            }
+            addr[r] = (uint64_t)lo << 56 | (runs.file_base[lo] + roff[r]);
+        }
+        if (value8) {
+            const uint32_t vl = text_vlen(vlen[r]), l = vl < 8 ? vl : 8;
+            const uint64_t p = vpos[r];
+            value8[r] = (p < bytes ? sel_gload64(text, bytes, p) : 0) & low_bytes_mask(l);
+            value_len[r] = (uint8_t)l;
+        }
+    }
+}
+
+}  // namespace bsdb

@@ -147,7 +147,21 @@ SIGNATURES = [
     ("bsdb_dev_db_locate_fixed", _i, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("bsdb_dev_db_locate_var", _i, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("bsdb_dev_db_gather", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    ("bsdb_text_max_records", _u64, [_u64]),
+    ("bsdb_dev_text_split", _i, [_vp, _vp, _u64, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_text_pack", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp,
+                                C.POINTER(_u64), _vp, _vp, _vp]),
+    ("bsdb_builder_add_dev_var", _i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("bsdb_text_set_chunk", _i, [_vp, _u64]),
+    ("bsdb_text_build", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, C.c_char_p, _i, _u32, _i, C.c_char_p, C.c_char_p, _vp,
+                             C.POINTER(_vp)]),
 ]
+
+TEXT_WORDS = 10
+# the text report's words in the header's order (uint64_t[BSDB_TEXT_WORDS])
+TEXT_FIELDS = ("lines", "records", "not_two_fields", "empty_key", "too_large", "key_bytes", "value_bytes", "max_key_len",
+               "max_value_len", "chunks")
+TEXT_MAX_KEY, TEXT_MAX_VALUE = 255, 32510  # Common.MAX_KEY_SIZE, Common.MAX_VALUE_SIZE
 
 BSDB_E2BIG = -7
 GET_WORDS = 6
@@ -256,6 +270,11 @@ def mph_sizes(n: int, width: int) -> dict:
     m, vw, vb, sw = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
     _check("bsdb_mph_sizes", lib().bsdb_mph_sizes(n, width, C.byref(m), C.byref(vw), C.byref(vb), C.byref(sw)))
     return {"num_buckets": m.value, "values_words": vw.value, "value_bits": vb.value, "sig_words": sw.value}
+
+
+def text_max_records(nbytes: int) -> int:
+    """bsdb_text_max_records: the most records `nbytes` of text can hold (host only)."""
+    return int(lib().bsdb_text_max_records(nbytes))
 
 
 def range_windows(n_global: int, width: int, e_lo: int, n_local: int):
@@ -925,6 +944,99 @@ class Context:
             db._h, _ptr(src), _ptr(voff), nq, _ptr(values), value_bytes, _stream(stream)))
         return values[:value_bytes]
 
+    # ---- text front end: lines of "key<sep>value" -> descriptors -> kv.db image
+    @staticmethod
+    def _sep(separator) -> int:
+        s = separator.encode("latin-1") if isinstance(separator, str) else bytes(separator)
+        if len(s) != 1:
+            raise ValueError("the separator is one byte")
+        return s[0]
+
+    def text_split(self, text, separator=" ", nbytes: Optional[int] = None, desc=None, report=None, stream=None):
+        """bsdb_dev_text_split: `text` a uint8 tensor at a 16-byte aligned
+        address.  Returns (desc, report): desc int32[4, cap] with rows kpos,
+        klen, vpos, vlen (cap >= text_max_records(nbytes)), the first
+        report[1] columns written in input order; report int64[TEXT_WORDS]
+        (zeroed by the caller when given) accumulates."""
+        import torch
+        if nbytes is None:
+            nbytes = text.numel()
+        cap = text_max_records(nbytes)
+        if desc is None:
+            desc = torch.empty((4, cap), dtype=torch.int32, device=text.device)
+        elif desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[0] != 4 or not desc.is_contiguous():
+            raise ValueError("desc is a contiguous int32[4, cap]")
+        if report is None:
+            report = torch.zeros(TEXT_WORDS, dtype=torch.int64, device=text.device)
+        elif report.dtype != torch.int64 or report.numel() < TEXT_WORDS:
+            raise ValueError("report int64[TEXT_WORDS]")
+        _check("bsdb_dev_text_split", lib().bsdb_dev_text_split(
+            self._h, _ptr(text), nbytes, self._sep(separator), desc.shape[1], _ptr(desc[0]), _ptr(desc[1]),
+            _ptr(desc[2]), _ptr(desc[3]), _ptr(report), _stream(stream)))
+        return desc, report
+
+    def text_pack(self, text, desc, count: int, partitions: int, part_sizes, approximate: bool = False,
+                  nbytes: Optional[int] = None, image=None, addr=None, blob=None, off=None, value8=None, value_len=None,
+                  stream=None) -> dict:
+        """bsdb_dev_text_pack of the first `count` descriptors of text_split.
+        The outputs are the caller's tensors or allocated here: image / blob /
+        value_len uint8 at any address, addr / off / value8 int64.  Returns
+        {"image", "run_bytes", "addr", "blob", "off", "value8", "value_len"},
+        each cut to what was written; run p is image[sum(run_bytes[:p]):][:run_bytes[p]]."""
+        import numpy as np
+        import torch
+        if nbytes is None:
+            nbytes = text.numel()
+        dev = text.device
+        sizes = np.ascontiguousarray(part_sizes, np.uint64)
+        if sizes.size != partitions:
+            raise ValueError("one size per partition")
+        if image is None:
+            image = torch.empty(nbytes + nbytes // 2 + 16, dtype=torch.uint8, device=dev)
+        if blob is None:
+            blob = torch.empty(nbytes + 16, dtype=torch.uint8, device=dev)
+        if addr is None:
+            addr = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        if off is None:
+            off = torch.empty(count + 1, dtype=torch.int64, device=dev)
+        if approximate and value8 is None:
+            value8 = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        if approximate and value_len is None:
+            value_len = torch.empty(max(count, 1), dtype=torch.uint8, device=dev)
+        if addr.numel() < count or off.numel() < count + 1 or (approximate and min(value8.numel(), value_len.numel()) < count):
+            raise ValueError("addr / value8 / value_len hold count entries, off count + 1")
+        runs = np.zeros(partitions, np.uint64)
+        blob_bytes = C.c_uint64()
+        _check("bsdb_dev_text_pack", lib().bsdb_dev_text_pack(
+            self._h, _ptr(text), nbytes, _ptr(desc[0]), _ptr(desc[1]), _ptr(desc[2]), _ptr(desc[3]), count, partitions,
+            sizes.ctypes.data, _ptr(image), image.numel(), runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(),
+            _ptr(off), C.byref(blob_bytes), _ptr(value8) if approximate else None,
+            _ptr(value_len) if approximate else None, _stream(stream)))
+        return {"image": image[: int(runs.sum())], "run_bytes": [int(x) for x in runs], "addr": addr[:count],
+                "blob": blob[: blob_bytes.value], "off": off[: count + 1],
+                "value8": value8[:count] if approximate else None, "value_len": value_len[:count] if approximate else None}
+
+    def text_set_chunk(self, nbytes: int = 0):
+        """Text bytes bsdb_text_build handles at a time (0 = default)."""
+        _check("bsdb_text_set_chunk", lib().bsdb_text_set_chunk(self._h, nbytes))
+
+    def text_build(self, paths, separator, kv_base: str, partitions: int, width: int, index_path: str,
+                   index_a_path: Optional[str] = None, approximate: bool = False):
+        """bsdb_text_build: (Mph, report dict).  A failure raises BsdbError
+        with the report so far in ``.text_report``."""
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        report = (C.c_uint64 * TEXT_WORDS)()
+        h = C.c_void_p()
+        rc = lib().bsdb_text_build(self._h, arr, len(paths), self._sep(separator), os.fsencode(kv_base), partitions,
+                                   width, 1 if approximate else 0, os.fsencode(index_path),
+                                   os.fsencode(index_a_path) if index_a_path else None, report, C.byref(h))
+        rep = {k: int(v) for k, v in zip(TEXT_FIELDS, report)}
+        if rc != BSDB_OK:
+            e = BsdbError("bsdb_text_build", rc)
+            e.text_report = rep
+            raise e
+        return Mph(h, self), rep
+
     def gen_keys_var(self, first: int, n: int, stream=None, offsets=None, blob=None):
         """Config C5 var-len keys on the device: (blob u8, offsets int64[n+1]).
         offsets / blob: the caller's tensors (blob.numel() is the capacity the
@@ -1249,6 +1361,15 @@ class Builder:
         vl = np.ascontiguousarray(vlen_np, np.uint8) if vlen_np is not None else None
         _check("bsdb_builder_add_var", lib().bsdb_builder_add_var(
             self._h, blob_np.ctypes.data, off_np.ctypes.data, n, _np_ptr(a), _np_ptr(v8), _np_ptr(vl)))
+
+    def add_dev_var(self, blob, off, addr=None, value8=None, vlen=None, stream=None):
+        """bsdb_builder_add_dev_var: the batch in device memory (torch
+        tensors): blob uint8, off int64[count + 1] into it, addr / value8
+        int64[count], vlen uint8[count]."""
+        count = off.numel() - 1
+        _check("bsdb_builder_add_dev_var", lib().bsdb_builder_add_dev_var(
+            self._h, _ptr(blob), _ptr(off), count, _ptr(addr) if addr is not None else None,
+            _ptr(value8) if value8 is not None else None, _ptr(vlen) if vlen is not None else None, _stream(stream)))
 
     def finish(self, width: int, index_path: Optional[str] = None, index_a_path: Optional[str] = None,
                passes: int = 0):

@@ -800,6 +800,102 @@ int bsdb_dev_db_locate_var(bsdb_db *db, const uint8_t *d_blob, uint64_t blob_byt
 int bsdb_dev_db_gather(bsdb_db *db, const uint64_t *d_src, const uint64_t *d_voff, uint64_t nq, uint8_t *d_values,
                        uint64_t value_bytes, void *stream);
 
+/* ---- text front end: "key<sep>value" lines -> records -> kv.db + database ----
+ * What tools/Builder.java:144-176 does one line per call on one thread per
+ * input file: split text into lines and fields, keep the lines that are
+ * records, write them in the compact kv.db layout ([kLen u8][vLen u16 BE][key]
+ * [value], SimpleCompactKVWriter.java:36-42) and hand their keys to the build.
+ *
+ * The record rule (BufferedReader.lines, String.split(sep), Builder.java:148-160):
+ *   lines    a line ends at "\n", at "\r" or at "\r\n"; a last line without a
+ *            terminator is a line; nothing follows the final terminator (the
+ *            empty text has 0 lines, "\n" one empty line).  Byte i starts a line
+ *            iff i == 0, or t[i-1] == '\n', or (t[i-1] == '\r' and t[i] != '\n').
+ *   fields   the line is split at every separator byte and trailing empty
+ *            fields are dropped; it is a record iff exactly two fields remain:
+ *            key = field 0, value = field 1.  Everything else counts as
+ *            not_two_fields.
+ *   then     a key of 0 bytes is dropped (empty_key; a DEVIATION: the reference
+ *            would put it, this library's writers take keys of 1..255 bytes);
+ *            a key over 255 or a value over 32 510 bytes (Common.MAX_VALUE_SIZE)
+ *            is dropped (too_large).
+ *   bytes    taken verbatim: bytes >= 0x80 and NUL are data.  Malformed UTF-8,
+ *            which Java's decoder would replace, is out of scope (a DEVIATION
+ *            for such input only).  The separator is ONE literal byte < 0x80
+ *            that is neither '\r' nor '\n' (else BSDB_EINVAL); a byte that
+ *            String.split would read as a regex meta-character ('|', '.', '*'
+ *            ...) is taken literally here (a DEVIATION).
+ *   order    kept records keep input order: files in the order given, then
+ *            lines in file order.
+ * The report is uint64_t[BSDB_TEXT_WORDS], ACCUMULATED by the dev_ call:
+ *   [0] lines  [1] records  [2] not_two_fields  [3] empty_key  [4] too_large
+ *   [5] key_bytes  [6] value_bytes  [7] max_key_len  [8] max_value_len
+ *   [9] chunks;   lines == records + not_two_fields + empty_key + too_large.
+ *
+ * bsdb_text_max_records: the most records `bytes` of text can hold,
+ *   bytes / 4 + 1 (host only).
+ * bsdb_dev_text_split: d_text (16-byte aligned, bytes < 2^32) on the device
+ *   -> the kept records' descriptors in input order: key at d_text[d_kpos[r]
+ *   .. + d_klen[r]), value at d_text[d_vpos[r] .. + d_vlen[r]); capacity >=
+ *   bsdb_text_max_records(bytes) entries each, else BSDB_EINVAL.  d_report
+ *   (8-byte aligned, zeroed by the caller) accumulates; [1] tells how many
+ *   descriptors were written.  Enqueued on `stream`; the call waits once for
+ *   the count kernel (the numbers of lines and separators size its
+ *   workspace), the rest is asynchronous.
+ * bsdb_dev_text_pack: `count` descriptors of that text -> the chunk's image,
+ *   the records back to back, cut by the PARTITION RULE into `partitions`
+ *   (1..128) contiguous runs, run p = records [p count / P, (p + 1) count / P)
+ *   (the reference leaves the assignment open, PartitionedKVWriter.java:82-96):
+ *   run p is to be appended to kv.db.<p> at h_part_size[p], its bytes come back
+ *   in h_run_bytes[p] (the runs lie in d_image in order, so they leave as P
+ *   plain copies); d_addr[r] = p << 56 | file offset of record r; d_blob /
+ *   d_off[count + 1] the packed keys with their offsets from 0 (*h_blob_bytes =
+ *   d_off[count]); d_value8 / d_value_len (both or neither) the index_a.db
+ *   payload: the first min(vLen, 8) value bytes, the rest 0, and that length.
+ *   d_image, d_blob and d_value_len may start at any address; nothing is written
+ *   outside the bytes reported.  BSDB_EINVAL when image_cap or blob_cap is too
+ *   small (nothing written; 1.5 x bytes + 16 and bytes + 16 always suffice) or
+ *   a file would pass 2^56 bytes.  The call returns with the sizes, so it waits
+ *   for its scans; the pack kernels are left running on `stream`.
+ * bsdb_builder_add_dev_var: bsdb_builder_add_var with the batch in device
+ *   memory (d_off[0 .. count] into d_blob, the record arrays as for the host
+ *   add).  The keys and offsets are copied device to device, the record arrays
+ *   to the builder's host arrays (and device arrays, when it keeps them); a
+ *   builder in spill mode takes the batch through host memory and the host add.
+ *   The caller's buffers are free when the call returns.  Builders of
+ *   variable-length keys only.
+ * bsdb_text_set_chunk: text bytes bsdb_text_build handles at a time (0 =
+ *   default 256 MiB; at least 64 KiB; capped so that a chunk's device footprint
+ *   fits half of the free device memory).
+ * bsdb_text_build: Builder's put loop and build(): every file of paths[0 ..
+ *   nfiles) is read a chunk at a time, cut after the chunk's last line end (the
+ *   rest is carried to the next chunk; chunks never span files, and a file's
+ *   unterminated last line does not join the next file), split, packed, its
+ *   runs appended to kv_base.<p> (created or truncated) and its keys added to a
+ *   streaming builder on the device; the finish writes index_path /
+ *   index_a_path as bsdb_builder_finish does.  `report` (host) is the whole
+ *   input's.  A line longer than the chunk returns BSDB_E2BIG (a DEVIATION: Java
+ *   takes lines of any length).  BSDB_EDUP comes back as from any build: the
+ *   kv.db files are complete then, so bsdb_kv_find_duplicates names the records.
+ *   The empty input builds the empty database.
+ * ------------------------------------------------------------------------- */
+#define BSDB_TEXT_WORDS 10
+uint64_t bsdb_text_max_records(uint64_t bytes);
+int bsdb_dev_text_split(bsdb_ctx *ctx, const uint8_t *d_text, uint64_t bytes, int separator, uint64_t capacity,
+                        uint32_t *d_kpos, uint32_t *d_klen, uint32_t *d_vpos, uint32_t *d_vlen, uint64_t *d_report,
+                        void *stream);
+int bsdb_dev_text_pack(bsdb_ctx *ctx, const uint8_t *d_text, uint64_t bytes, const uint32_t *d_kpos,
+                       const uint32_t *d_klen, const uint32_t *d_vpos, const uint32_t *d_vlen, uint64_t count,
+                       int partitions, const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap,
+                       uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off,
+                       uint64_t *h_blob_bytes, uint64_t *d_value8, uint8_t *d_value_len, void *stream);
+int bsdb_builder_add_dev_var(bsdb_builder *b, const uint8_t *d_blob, const uint64_t *d_off, uint64_t count,
+                             const uint64_t *d_addr, const uint64_t *d_value8, const uint8_t *d_vlen, void *stream);
+int bsdb_text_set_chunk(bsdb_ctx *ctx, uint64_t bytes);
+int bsdb_text_build(bsdb_ctx *ctx, const char *const *paths, int nfiles, int separator, const char *kv_base,
+                    int partitions, uint32_t width, int approximate, const char *index_path, const char *index_a_path,
+                    uint64_t *report /* BSDB_TEXT_WORDS */, bsdb_mph **out);
+
 #ifdef __cplusplus
 }
 #endif
