@@ -3,10 +3,12 @@
 The reference's command-line ``Builder`` (tools/Builder.java:144-176) reads
 its input files line by line, splits every line at the separator and puts the
 lines that are records; ``build()`` then makes the hash and the index.  Here
-the whole of that is one native call, ``bsdb_text_build``: the text is split
-into lines and fields, the records packed into the compact kv.db layout and
-their keys handed to the streaming builder by gfx950 kernels
-(bsdb_amd/csrc/text_kernels.hip).  There is no CPU fallback for the parse.
+the whole of that is one native call, ``bsdb_text_build_layout``: the text is
+split into lines and fields, the records packed into the compact kv.db layout
+(or, with ``layout="blocked"``, placed into the blocks of the reference's
+default layout) and their keys handed to the streaming builder by gfx950
+kernels (bsdb_amd/csrc/text_kernels.hip, text_blocked_kernels.hip).  There is
+no CPU fallback for the parse.
 
 ``build_text`` writes the file set of ``bsdb_amd.writer.BSDBWriter``:
 kv.db.<p>, config.properties, hash.dump, index.db, index_a.db.
@@ -19,6 +21,7 @@ one literal byte (never a regular expression), a line must fit one chunk.
 Command line, mirroring ``Builder``'s flags::
 
     python -m bsdb_amd.builder -i INPUT [-i INPUT ...] -o OUT_DIR [-s SEP] [-cb BITS] [-a] [-v] [-p PARTITIONS]
+                               [-l {compact,blocked}] [-bs BLOCK_SIZE]
 """
 from __future__ import annotations
 
@@ -50,12 +53,19 @@ def input_files(inputs) -> list:
     return files
 
 
-def _write_config(out_dir: str, report: dict, approximate: bool, checksum_bits: int):
+LAYOUTS = {"compact": 0, "blocked": 1}
+
+
+def _write_config(out_dir: str, report: dict, approximate: bool, checksum_bits: int, layout: str = "compact",
+                  block_size: int = 4096):
     """config.properties with the keys of BSDBWriter._write_config, the
-    statistics taken from the text report."""
+    statistics taken from the text report.  The blocked layout's block size
+    goes where BSDBReader reads it: kv.compress.block.size."""
     n = report["records"]
+    blocked = layout == "blocked"
     props = {
-        "kv.compressed": "false", "kv.compact": "true", "kv.compress.block.size": 8192,
+        "kv.compressed": "false", "kv.compact": "false" if blocked else "true",
+        "kv.compress.block.size": block_size if blocked else 8192,
         "index.approximate": str(bool(approximate)).lower(), "hash.checksum.bits": checksum_bits,
         "kv.count": n, "kv.key.len.max": report["max_key_len"],
         "kv.key.len.avg": report["key_bytes"] / n if n else 0.0, "kv.value.len.max": report["max_value_len"],
@@ -66,13 +76,16 @@ def _write_config(out_dir: str, report: dict, approximate: bool, checksum_bits: 
             f.write(f"{k} = {v}\n")
 
 
-def _duplicate_error(ctx: Context, kv_base: str, partitions: int) -> DuplicateKeyError:
+def _duplicate_error(ctx: Context, kv_base: str, partitions: int, fmt: int = 0, block_size: int = 4096) -> DuplicateKeyError:
     """The duplicate finder over the kv.db files the failed build completed,
-    with up to 16 colliding keys read back at the reported addresses."""
-    rep = ctx.kv_find_duplicates(kv_base, partitions)
+    with up to 16 colliding keys read back at the reported addresses (blocked:
+    the block's page in bits 16-47, the offset in the low 16 bits)."""
+    rep = ctx.kv_find_duplicates(kv_base, partitions, fmt, block_size)
     keys, seen = [], set()
     for addr in rep["pairs"].reshape(-1).tolist():
         p, off = int(addr) >> 56, int(addr) & ((1 << 56) - 1)
+        if fmt == 1:
+            off = ((int(addr) >> 16) & 0xFFFFFFFF) * 4096 + (int(addr) & 0xFFFF)
         with open(f"{kv_base}.{p}", "rb") as f:
             f.seek(off)
             head = f.read(3)
@@ -88,12 +101,18 @@ def _duplicate_error(ctx: Context, kv_base: str, partitions: int) -> DuplicateKe
 
 
 def build_text(inputs, out_dir: str, separator=" ", checksum_bits: int = 4, approximate: bool = False,
-               partitions: int = 8, verify: bool = False, device: int = 0, chunk_bytes: Optional[int] = None) -> dict:
+               partitions: int = 8, verify: bool = False, device: int = 0, chunk_bytes: Optional[int] = None,
+               layout: str = "compact", block_size: int = 4096) -> dict:
     """Builds the database of the records in ``inputs`` into ``out_dir`` and
-    returns the text report (native.TEXT_FIELDS).  ``verify=True`` checks the
+    returns the text report (native.TEXT_FIELDS).  ``layout``: "compact" (the
+    reference's -c) or "blocked" (the reference's default) in blocks of
+    ``block_size`` bytes.  ``verify=True`` checks the
     finished files on the device (Mph.verify_kv) and raises VerifyError when
     they are not clean.  A duplicate key raises DuplicateKeyError (``.keys``:
     up to 16 of them)."""
+    if layout not in LAYOUTS:
+        raise ValueError("layout is 'compact' or 'blocked'")
+    fmt = LAYOUTS[layout]
     files = input_files(inputs)
     os.makedirs(out_dir, exist_ok=True)
     kv = os.path.join(out_dir, "kv.db")
@@ -102,16 +121,17 @@ def build_text(inputs, out_dir: str, separator=" ", checksum_bits: int = 4, appr
         if chunk_bytes is not None:
             ctx.text_set_chunk(chunk_bytes)
         try:
-            mph, report = ctx.text_build(files, separator, kv, partitions, checksum_bits, index, index_a, approximate)
+            mph, report = ctx.text_build(files, separator, kv, partitions, checksum_bits, index, index_a, approximate,
+                                         fmt=fmt, block_size=block_size)
         except BsdbError as e:
             if e.code != BSDB_EDUP:
                 raise
-            raise _duplicate_error(ctx, kv, partitions) from e
+            raise _duplicate_error(ctx, kv, partitions, fmt, block_size) from e
         try:
-            _write_config(out_dir, report, approximate, checksum_bits)
+            _write_config(out_dir, report, approximate, checksum_bits, layout, block_size)
             mph.dump(os.path.join(out_dir, "hash.dump"))
             if verify:
-                rep = mph.verify_kv(kv, partitions, index, index_a, approximate)
+                rep = mph.verify_kv(kv, partitions, index, index_a, approximate, fmt=fmt, block_size=block_size)
                 if not rep["ok"]:
                     raise VerifyError(rep)
         finally:
@@ -119,12 +139,13 @@ def build_text(inputs, out_dir: str, separator=" ", checksum_bits: int = 4, appr
     return report
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(
         prog="python -m bsdb_amd.builder",
         description="Build a database from text files of key<separator>value lines on the GPU. "
-                    "The kv.db layout is always the compact one (the reference's -c); "
-                    "compressed records (-z) and compressed inputs are not supported.")
+                    "Without -l the kv.db layout is always the compact one (the reference's -c); "
+                    "-l blocked writes the reference's default layout. "
+                    "Compressed records (-z) and compressed inputs are not supported.")
     ap.add_argument("-i", "--input", action="append", required=True,
                     help="input file or directory (its *.txt files, sorted by name); may be given more than once")
     ap.add_argument("-o", "--output", default="./rdb/", help="output directory, default ./rdb/")
@@ -133,12 +154,21 @@ def main(argv=None) -> int:
     ap.add_argument("-a", "--approximate", action="store_true", help="approximate mode: index_a.db holds the first 8 value bytes")
     ap.add_argument("-v", "--verify", action="store_true", help="verify the generated index on the device")
     ap.add_argument("-p", "--partitions", type=int, default=8, help="kv.db partition files, 1..128, default 8")
+    ap.add_argument("-l", "--layout", choices=sorted(LAYOUTS), default="compact",
+                    help="kv.db layout, default compact; the reference's own default is blocked")
+    ap.add_argument("-bs", "--block-size", type=int, default=4096,
+                    help="block bytes of the blocked layout: a multiple of 4096 up to 65536, default 4096")
     ap.add_argument("-q", "--quiet", action="store_true", help="print nothing")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
     files = []
     for i in a.input:
         files += input_files(i)
-    report = build_text(files, a.output, a.separator, a.checksum_bits, a.approximate, a.partitions, a.verify)
+    report = build_text(files, a.output, a.separator, a.checksum_bits, a.approximate, a.partitions, a.verify,
+                        layout=a.layout, block_size=a.block_size)
     if not a.quiet:
         print(" ".join(f"{k}={v}" for k, v in report.items()))
     return 0

@@ -9,8 +9,8 @@
 // capi_comm / mph / multi / passes / builder / kv / verify.hip, capi_dup.hip
 // (which keys are duplicates, with its plan dup_plan.hpp), capi_get.hip
 // (batched get of a resident database, with its plan get_plan.hpp),
-// capi_text.hip (text lines into records, kv.db files and a database, with its
-// plan text_plan.hpp).
+// capi_text.hip (text lines into records, kv.db files in the compact or the
+// blocked layout and a database, with its plan text_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -52,6 +52,7 @@
 #include "dup_plan.hpp"
 #include "get_kernels.hip"
 #include "text_kernels.hip"
+#include "text_blocked_kernels.hip"
 
 using namespace bsdb;
 
@@ -177,6 +178,7 @@ struct bsdb_ctx {
     // records' sizes and the image scan
     DevBuf t_cnt{bufs, true}, t_off{bufs, true}, t_ls{bufs, true}, t_sp{bufs, true}, t_keep{bufs, true}, t_scan{bufs, true};
     DevBuf t_size{bufs, true}, t_roff{bufs, true};
+    DevBuf t_blk{bufs, true};  // the blocked layout's placement workspace (text_place_workspace)
     uint64_t text_chunk = 0;  // bsdb_text_set_chunk (0 = default)
     // live profiling: event pairs per launch, per kind
     bool profiling = false;

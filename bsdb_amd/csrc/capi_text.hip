@@ -3,7 +3,8 @@
 // capi_get.hip.
 //   bsdb_dev_text_split / bsdb_dev_text_pack   the kernels on device buffers
 //   bsdb_builder_add_dev_var                   a batch in device memory into the streaming builder
-//   bsdb_text_set_chunk / bsdb_text_build      files of text lines -> kv.db files + index files
+//   bsdb_dev_text_pack_blocked                 the pack into the blocked layout (text_blocked_kernels.hip)
+//   bsdb_text_set_chunk / bsdb_text_build(_layout)   files of text lines -> kv.db files + index files
 // What Builder's put loop and build() do (tools/Builder.java:144-176) one line
 // per call on one thread per input file.
 
@@ -126,6 +127,93 @@ int text_pack_impl(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const Tex
         k_text_outputs<<<lgrid, 256, 0, s>>>(runs, d_text, bytes, d.vpos, d.vlen, roff, count, d_addr, d_value8, d_value_len);
     if ((rc = launch_status())) return rc;
     for (int p = 0; p < partitions; ++p) h_run_bytes[p] = at[p + 1] - at[p];
+    if (h_blob_bytes) *h_blob_bytes = blob_bytes;
+    return BSDB_OK;
+}
+
+// text_pack_impl for the blocked layout (text_blocked_kernels.hip): blocks of
+// `B` bytes, run p appended to a file of h_part_size[p] bytes (a multiple of
+// 4096).  Waits once, for the placement: the runs' bytes are the events' sums
+// plus the block each run with a small record leaves open at its end.
+int text_pack_blocked_impl(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const TextDesc &d, uint64_t count, int partitions,
+                           uint32_t B, const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap,
+                           uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off,
+                           uint64_t *h_blob_bytes, uint64_t *d_value8, uint8_t *d_value_len, hipStream_t s) {
+    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = 0;
+    if (h_blob_bytes) *h_blob_bytes = 0;
+    if (!count) {
+        if (d_off) HIP_OK(hipMemsetAsync(d_off, 0, 8, s));
+        return BSDB_OK;
+    }
+    int rc;
+    if ((rc = c->t_size.grow(2 * 4 * count)) || (rc = c->t_blk.grow(text_place_workspace(count)))) return rc;
+    const uint32_t tiles = (uint32_t)((count + TEXT_TILE - 1) / TEXT_TILE);
+    uint32_t *rsize = c->t_size.as<uint32_t>(), *ksize = rsize + count;
+    // the workspace, 8-byte arrays first
+    uint64_t *S = c->t_blk.as<uint64_t>(), *E = S + count + 1, *PS = E + count + 1, *PL = PS + count + 1;
+    uint2 *exl = reinterpret_cast<uint2 *>(PL + count + 1);
+    uint32_t *ssize = reinterpret_cast<uint32_t *>(exl + count), *next = ssize + count, *ev = next + count, *boff = ev + count,
+             *bend = boff + count, *entry = bend + count, *carry = entry + tiles;
+    const uint32_t lgrid = text_lane_grid(count, c->num_cus);
+    TextRuns runs{};
+    runs.partitions = (uint32_t)partitions;
+    for (int p = 0; p <= partitions; ++p) runs.bound[p] = text_run_bound(count, (uint32_t)partitions, (uint32_t)p);
+    k_blk_sizes<<<lgrid, 256, 0, s>>>(d.klen, d.vlen, count, B, rsize, ksize, ssize);
+    if ((rc = text_scan(c, ssize, count, S, s))) return rc;
+    if (d_off && (rc = text_scan(c, ksize, count, d_off, s))) return rc;
+    HIP_OK(hipMemsetAsync(entry, 0, 2 * 4 * (size_t)tiles, s));
+    k_blk_tile<<<tiles, 256, 0, s>>>(runs, S, count, B, next, exl);
+    k_blk_chase<<<(uint32_t)partitions, 64, 0, s>>>(runs, exl, count, tiles, entry, carry);
+    k_blk_flags<<<tiles, 256, 0, s>>>(runs, S, rsize, next, entry, carry, count, B, ev, boff, bend);
+    if ((rc = text_scan(c, ev, count, E, s))) return rc;
+    uint64_t e_at[TEXT_MAX_PARTS + 1] = {}, s_at[TEXT_MAX_PARTS + 1] = {}, blob_bytes = 0;
+    for (int p = 0; p <= partitions; ++p) {
+        HIP_OK(hipMemcpyAsync(&e_at[p], E + runs.bound[p], 8, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(&s_at[p], S + runs.bound[p], 8, hipMemcpyDeviceToHost, s));
+    }
+    if (d_off) HIP_OK(hipMemcpyAsync(&blob_bytes, d_off + count, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    TextBlockedRuns br{};
+    uint64_t run[TEXT_MAX_PARTS] = {}, image_bytes = 0;
+    for (int p = 0; p < partitions; ++p) {
+        run[p] = e_at[p + 1] - e_at[p] + (s_at[p + 1] > s_at[p] ? B : 0);
+        if (h_part_size[p] > TEXT_MAX_FILE_BLOCKED || run[p] > TEXT_MAX_FILE_BLOCKED - h_part_size[p]) return BSDB_EINVAL;
+        br.image_base[p] = image_bytes;
+        br.file_size[p] = h_part_size[p];
+        image_bytes += run[p];
+    }
+    if ((d_image && image_bytes > image_cap) || (d_blob && blob_bytes > blob_cap)) return BSDB_EINVAL;
+    if (d_image || d_addr)
+        k_blk_place<<<text_lane_grid(count + 1, c->num_cus), 256, 0, s>>>(runs, br, E, rsize, boff, bend, count, B, image_bytes,
+                                                                           PS, PL, d_addr);
+    TextPack a{};
+    a.text = d_text;
+    a.bytes = bytes;
+    a.kpos = d.kpos;
+    a.klen = d.klen;
+    a.vpos = d.vpos;
+    a.vlen = d.vlen;
+    a.count = count;
+    if (d_image && image_bytes) {
+        TextPackBlocked b{};
+        b.t = a;
+        b.t.dst = d_image;
+        b.t.out_bytes = image_bytes;
+        b.PS = PS;
+        b.PL = PL;
+        b.B = B;
+        k_text_pack_blocked<<<text_pack_grid(image_bytes, (uint32_t)((uintptr_t)d_image & 15), c->num_cus), 256, 0, s>>>(b);
+    }
+    if (d_blob && blob_bytes) {
+        a.off = d_off;
+        a.dst = d_blob;
+        a.out_bytes = blob_bytes;
+        k_text_pack<false><<<text_pack_grid(blob_bytes, (uint32_t)((uintptr_t)d_blob & 15), c->num_cus), 256, 0, s>>>(a);
+    }
+    if (d_value8)
+        k_text_outputs<<<lgrid, 256, 0, s>>>(runs, d_text, bytes, d.vpos, d.vlen, nullptr, count, nullptr, d_value8, d_value_len);
+    if ((rc = launch_status())) return rc;
+    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = run[p];
     if (h_blob_bytes) *h_blob_bytes = blob_bytes;
     return BSDB_OK;
 }
@@ -318,6 +406,32 @@ int bsdb_dev_text_pack(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const
                           d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len, s);
 }
 
+uint64_t bsdb_text_image_max(uint64_t bytes, int partitions, int format, uint32_t block_size) {
+    return format == 1 ? text_image_max_blocked(bytes, partitions, block_size) : text_image_max(bytes);
+}
+
+int bsdb_dev_text_pack_blocked(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const uint32_t *d_kpos, const uint32_t *d_klen,
+                               const uint32_t *d_vpos, const uint32_t *d_vlen, uint64_t count, int partitions,
+                               uint32_t block_size, const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap,
+                               uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off,
+                               uint64_t *h_blob_bytes, uint64_t *d_value8, uint8_t *d_value_len, void *stream) {
+    if (!c || bytes > TEXT_MAX_BYTES || (bytes && !d_text) || !aligned16(d_text) || count > text_max_records(bytes) ||
+        partitions < 1 || partitions > TEXT_MAX_PARTS || text_bad_block_size(block_size) || !h_part_size || !h_run_bytes ||
+        (count && (!d_kpos || !d_klen || !d_vpos || !d_vlen)) ||
+        (((uintptr_t)d_kpos | (uintptr_t)d_klen | (uintptr_t)d_vpos | (uintptr_t)d_vlen) & 3) || (!d_blob != !d_off) ||
+        (!d_value8 != !d_value_len) || (((uintptr_t)d_addr | (uintptr_t)d_off | (uintptr_t)d_value8) & 7))
+        return BSDB_EINVAL;
+    for (int p = 0; p < partitions; ++p)
+        if ((h_part_size[p] & (TEXT_PAGE - 1)) || h_part_size[p] > TEXT_MAX_FILE_BLOCKED) return BSDB_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    hipStream_t s = pick(c, stream);
+    Ordered ord(c, s);
+    const TextDesc d{d_kpos, d_klen, d_vpos, d_vlen};
+    return text_pack_blocked_impl(c, d_text, bytes, d, count, partitions, block_size, h_part_size, d_image, image_cap,
+                                  h_run_bytes, d_addr, d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len, s);
+}
+
 int bsdb_builder_add_dev_var(bsdb_builder *b, const uint8_t *d_blob, const uint64_t *d_off, uint64_t count,
                              const uint64_t *d_addr, const uint64_t *d_value8, const uint8_t *d_vlen, void *stream) {
     if (!b || b->key_len || (count && (!d_blob || !d_off)) ||
@@ -336,9 +450,18 @@ int bsdb_text_set_chunk(bsdb_ctx *c, uint64_t bytes) {
 int bsdb_text_build(bsdb_ctx *c, const char *const *paths, int nfiles, int sep, const char *kv_base, int partitions,
                     uint32_t width, int approximate, const char *index_path, const char *index_a_path, uint64_t *report,
                     bsdb_mph **out) {
+    return bsdb_text_build_layout(c, paths, nfiles, sep, kv_base, partitions, 0, 0, width, approximate, index_path, index_a_path,
+                                  report, out);
+}
+
+int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, int sep, const char *kv_base, int partitions,
+                           int format, uint32_t block_size, uint32_t width, int approximate, const char *index_path,
+                           const char *index_a_path, uint64_t *report, bsdb_mph **out) {
     if (!c || nfiles < 0 || (nfiles && !paths) || text_bad_separator(sep) || !kv_base || partitions < 1 ||
-        partitions > TEXT_MAX_PARTS || width > 64 || !index_path || (approximate && !index_a_path) || !report || !out)
+        partitions > TEXT_MAX_PARTS || width > 64 || !index_path || (approximate && !index_a_path) || !report || !out ||
+        (format != 0 && format != 1) || (format == 1 && text_bad_block_size(block_size)))
         return BSDB_EINVAL;
+    const bool blocked = format == 1;
     for (int f = 0; f < nfiles; ++f)
         if (!paths[f]) return BSDB_EINVAL;
     *out = nullptr;
@@ -365,7 +488,8 @@ int bsdb_text_build(bsdb_ctx *c, const char *const *paths, int nfiles, int sep, 
         HIP_OK(hipSetDevice(c->device));
         size_t free_b = 0, total_b = 0;
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        chunk = text_chunk_bytes(c->text_chunk, free_b);
+        chunk = blocked ? text_chunk_bytes_blocked(c->text_chunk, free_b, partitions, block_size)
+                        : text_chunk_bytes(c->text_chunk, free_b);
         int rc = bufs.report.grow(8 * TW_WORDS);
         if (rc) return rc;
         HIP_OK(hipMemsetAsync(bufs.report.p, 0, 8 * TW_WORDS, c->stream));
@@ -422,16 +546,22 @@ int bsdb_text_build(bsdb_ctx *c, const char *const *paths, int nfiles, int sep, 
                 records = report[TW_RECORDS];
                 if (k > cap) return BSDB_EIO;
                 if (k) {
-                    if ((rc = bufs.image.grow(text_image_max(cut))) || (rc = bufs.blob.grow(text_blob_max(cut))) ||
+                    const uint64_t image_max = blocked ? text_image_max_blocked(cut, partitions, block_size) : text_image_max(cut);
+                    if ((rc = bufs.image.grow(image_max)) || (rc = bufs.blob.grow(text_blob_max(cut))) ||
                         (rc = bufs.off.grow(8 * (k + 1))) || (rc = bufs.addr.grow(8 * k)) ||
                         (approximate && ((rc = bufs.v8.grow(8 * k)) || (rc = bufs.vl.grow(k)))))
                         return rc;
-                    if ((rc = text_pack_impl(c, bufs.text.as<const uint8_t>(), cut, d, k, partitions, part_size,
-                                             bufs.image.as<uint8_t>(), text_image_max(cut), run_bytes,
-                                             bufs.addr.as<uint64_t>(), bufs.blob.as<uint8_t>(), text_blob_max(cut),
-                                             bufs.off.as<uint64_t>(), &blob_bytes, approximate ? bufs.v8.as<uint64_t>() : nullptr,
-                                             approximate ? bufs.vl.as<uint8_t>() : nullptr, s)))
-                        return rc;
+                    uint64_t *const v8 = approximate ? bufs.v8.as<uint64_t>() : nullptr;
+                    uint8_t *const vl = approximate ? bufs.vl.as<uint8_t>() : nullptr;
+                    rc = blocked ? text_pack_blocked_impl(c, bufs.text.as<const uint8_t>(), cut, d, k, partitions, block_size,
+                                                          part_size, bufs.image.as<uint8_t>(), image_max, run_bytes,
+                                                          bufs.addr.as<uint64_t>(), bufs.blob.as<uint8_t>(), text_blob_max(cut),
+                                                          bufs.off.as<uint64_t>(), &blob_bytes, v8, vl, s)
+                                 : text_pack_impl(c, bufs.text.as<const uint8_t>(), cut, d, k, partitions, part_size,
+                                                  bufs.image.as<uint8_t>(), image_max, run_bytes, bufs.addr.as<uint64_t>(),
+                                                  bufs.blob.as<uint8_t>(), text_blob_max(cut), bufs.off.as<uint64_t>(),
+                                                  &blob_bytes, v8, vl, s);
+                    if (rc) return rc;
                     for (int p = 0; p < partitions; ++p) image_bytes += run_bytes[p];
                     try {
                         if (himg.size() < image_bytes) himg.resize(image_bytes);

@@ -4,7 +4,10 @@
 // footprint once its lines and separators are counted (text_footprint), the
 // chunk size (text_chunk_bytes), the runs of the partition rule
 // (text_run_bound), where a buffer of a file is cut (text_cut), and the
-// verdict on one line (text_verdict), which the records kernel calls too.
+// verdict on one line (text_verdict), which the records kernel calls too; for
+// the blocked layout the placement rule stated sequentially
+// (text_place_blocked), the image's bound (text_image_max_blocked) and the
+// footprint and chunk size with the placement's workspace.
 // C++17 without HIP or getenv, so the arithmetic runs (and is checked,
 // tests/text_plan_check.cpp) without a GPU.
 //   tools/Builder.java:144-176 (BufferedReader.lines, String.split(sep), put)
@@ -122,6 +125,106 @@ inline uint64_t text_cut(const uint8_t *buf, uint64_t fill, bool eof) {
         if (b == '\r' && i < fill && buf[i] != '\n') return i;
     }
     return 0;
+}
+
+// ---- the blocked layout (BlockedKVWriter.java:45-74, :134-136) ------------
+// One run (the records of one partition in one chunk, in input order) into
+// blocks of B bytes appended to a file that holds F bytes.  size = 3 + kLen +
+// vLen.  A record with size > B is LARGE: a block of its own of ceil(size /
+// 4096) pages, appended at once, ahead of the block that is open.  A small
+// record that does not fit the rest of the open block closes it (the block is
+// appended at the file's end) and opens a new one; a record that exactly fills
+// the block leaves it open.  The run's end closes the open block (deviation 6
+// of the header: the reference's block lives on until finish).
+constexpr uint32_t TEXT_PAGE = 4096;
+constexpr uint32_t TEXT_MAX_BLOCK = 65536;               // the address has 16 bits of offset
+constexpr uint64_t TEXT_MAX_FILE_BLOCKED = 1ull << 44;   // ... and 32 bits of pages
+constexpr uint32_t TEXT_TILE = 2048;                     // records of one workgroup of the placement kernels
+constexpr uint32_t TEXT_MAX_RECORD = 3 + TEXT_MAX_KEY + TEXT_MAX_VALUE;  // 32 768
+
+BSDB_HD inline bool text_bad_block_size(uint32_t B) { return B < TEXT_PAGE || B > TEXT_MAX_BLOCK || (B & (TEXT_PAGE - 1)); }
+BSDB_HD inline uint32_t text_large_block(uint32_t size) { return (size + TEXT_PAGE - 1) & ~(TEXT_PAGE - 1); }
+
+struct TextPlaced {
+    uint64_t block_pos;    // file position of the record's block
+    uint32_t block_bytes;  // B, or a large record's pages
+    uint32_t offset;       // of the record in its block
+};
+
+// The rule, one record per step: the specification of the placement kernels
+// (tests/text_blocked_check.cpp holds it against a byte-level emulation of
+// writeRecord / flushBlocks).  Returns the bytes the run appends; `out` may be
+// null.  sizes[i] in 4 .. 32 768.
+inline uint64_t text_place_blocked(const uint32_t *sizes, uint64_t count, uint32_t B, uint64_t F, TextPlaced *out) {
+    uint64_t end = F;          // the file's end
+    uint32_t fill = 0;         // bytes in the open block
+    bool open = false;
+    uint64_t first = 0;        // the open block's first record
+    auto close = [&](uint64_t upto) {
+        for (uint64_t j = first; out && j < upto; ++j)
+            if (sizes[j] <= B) out[j].block_pos = end;
+        end += B;
+        open = false;
+    };
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t size = sizes[i];
+        if (size > B) {
+            if (out) out[i] = {end, text_large_block(size), 0};
+            end += text_large_block(size);
+            continue;
+        }
+        if (open && B - fill < size) close(i);
+        if (!open) {
+            open = true;
+            fill = 0;
+            first = i;
+        }
+        if (out) out[i] = {0, B, fill};
+        fill += size;
+    }
+    if (open) close(count);
+    return end - F;
+}
+
+// An upper bound of the blocked image of a chunk of `bytes` text bytes.  The
+// records themselves take R <= bytes + bytes / 4 + 2 bytes (text_image_max's
+// argument).  In one run, the first record of a block did not fit the block
+// before it, so two consecutive blocks hold more than B bytes together: n
+// blocks of a run that hold Rs bytes have floor(n / 2) disjoint such pairs,
+// Rs > (n - 1) / 2 x B, n x B < 2 Rs + B: the last, partial block of each run
+// costs at most B, the others at most twice what they hold.  A large record
+// (size > B >= 4096) gets less than size + 4096 < 2 x size.  Together:
+// < 2 R + partitions x B.
+inline uint64_t text_image_max_blocked(uint64_t bytes, int partitions, uint32_t B) {
+    return 2 * (bytes + bytes / 4 + 2) + (uint64_t)std::max(1, partitions) * B + 16;
+}
+
+// The placement's workspace for r records: the small sizes and their scan,
+// next, (last, exit), the events and their scan, each record's block offset
+// and block end, the two position lists, and entry + carry per tile.
+inline uint64_t text_place_workspace(uint64_t r) {
+    const uint64_t tiles = r / TEXT_TILE + 1;
+    return 4 * r + 8 * (r + 1) + 4 * r + 8 * r + 4 * r + 8 * (r + 1) + 4 * r + 4 * r + 2 * 8 * (r + 1) + 2 * 4 * tiles + 64;
+}
+
+// text_footprint with the blocked image and the placement's workspace: never
+// below the compact footprint.
+inline TextFootprint text_footprint_blocked(uint64_t bytes, uint64_t lines, uint64_t seps, bool approximate, int partitions,
+                                            uint32_t B) {
+    TextFootprint f = text_footprint(bytes, lines, seps, approximate);
+    const uint64_t more = text_image_max_blocked(bytes, partitions, B) - text_image_max(bytes) +
+                          text_place_workspace(text_max_records(bytes));
+    f.pack += more;
+    f.total += more;
+    return f;
+}
+
+inline uint64_t text_chunk_bytes_blocked(uint64_t requested, uint64_t free_bytes, int partitions, uint32_t B) {
+    uint64_t c = requested ? requested : TEXT_DEFAULT_CHUNK;
+    c = std::min<uint64_t>(std::max<uint64_t>(c, TEXT_MIN_CHUNK), TEXT_MAX_BYTES & ~15ull);
+    while (c > TEXT_MIN_CHUNK && text_footprint_blocked(c, c, c, true, partitions, B).total > free_bytes / 2)
+        c = std::max<uint64_t>(TEXT_MIN_CHUNK, c / 2);
+    return c;
 }
 
 // The separator: one literal byte below 0x80 that ends no line.

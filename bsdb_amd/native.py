@@ -155,6 +155,11 @@ SIGNATURES = [
     ("bsdb_text_set_chunk", _i, [_vp, _u64]),
     ("bsdb_text_build", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, C.c_char_p, _i, _u32, _i, C.c_char_p, C.c_char_p, _vp,
                              C.POINTER(_vp)]),
+    ("bsdb_text_image_max", _u64, [_u64, _i, _i, _u32]),
+    ("bsdb_dev_text_pack_blocked", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _i, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
+                                        _vp, C.POINTER(_u64), _vp, _vp, _vp]),
+    ("bsdb_text_build_layout", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, C.c_char_p, _i, _i, _u32, _u32, _i, C.c_char_p,
+                                    C.c_char_p, _vp, C.POINTER(_vp)]),
 ]
 
 TEXT_WORDS = 10
@@ -294,6 +299,11 @@ def _stream(stream) -> Optional[int]:
     if stream is None:
         return torch.cuda.current_stream().cuda_stream
     return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+
+def text_image_max(nbytes: int, partitions: int = 1, fmt: int = 0, block_size: int = 4096) -> int:
+    """bsdb_text_image_max: an upper bound of the image of `nbytes` of text (host only)."""
+    return int(lib().bsdb_text_image_max(nbytes, partitions, fmt, block_size))
 
 
 class Context:
@@ -977,8 +987,10 @@ class Context:
 
     def text_pack(self, text, desc, count: int, partitions: int, part_sizes, approximate: bool = False,
                   nbytes: Optional[int] = None, image=None, addr=None, blob=None, off=None, value8=None, value_len=None,
-                  stream=None) -> dict:
-        """bsdb_dev_text_pack of the first `count` descriptors of text_split.
+                  stream=None, block_size: Optional[int] = None) -> dict:
+        """bsdb_dev_text_pack of the first `count` descriptors of text_split;
+        with `block_size`, bsdb_dev_text_pack_blocked: the blocked layout in
+        blocks of that many bytes (part_sizes multiples of 4096).
         The outputs are the caller's tensors or allocated here: image / blob /
         value_len uint8 at any address, addr / off / value8 int64.  Returns
         {"image", "run_bytes", "addr", "blob", "off", "value8", "value_len"},
@@ -992,7 +1004,8 @@ class Context:
         if sizes.size != partitions:
             raise ValueError("one size per partition")
         if image is None:
-            image = torch.empty(nbytes + nbytes // 2 + 16, dtype=torch.uint8, device=dev)
+            image = torch.empty(text_image_max(nbytes, partitions, 0 if block_size is None else 1, block_size or 0),
+                                dtype=torch.uint8, device=dev)
         if blob is None:
             blob = torch.empty(nbytes + 16, dtype=torch.uint8, device=dev)
         if addr is None:
@@ -1007,11 +1020,14 @@ class Context:
             raise ValueError("addr / value8 / value_len hold count entries, off count + 1")
         runs = np.zeros(partitions, np.uint64)
         blob_bytes = C.c_uint64()
-        _check("bsdb_dev_text_pack", lib().bsdb_dev_text_pack(
-            self._h, _ptr(text), nbytes, _ptr(desc[0]), _ptr(desc[1]), _ptr(desc[2]), _ptr(desc[3]), count, partitions,
-            sizes.ctypes.data, _ptr(image), image.numel(), runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(),
-            _ptr(off), C.byref(blob_bytes), _ptr(value8) if approximate else None,
-            _ptr(value_len) if approximate else None, _stream(stream)))
+        head = (self._h, _ptr(text), nbytes, _ptr(desc[0]), _ptr(desc[1]), _ptr(desc[2]), _ptr(desc[3]), count, partitions)
+        tail = (sizes.ctypes.data, _ptr(image), image.numel(), runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(),
+                _ptr(off), C.byref(blob_bytes), _ptr(value8) if approximate else None,
+                _ptr(value_len) if approximate else None, _stream(stream))
+        if block_size is None:
+            _check("bsdb_dev_text_pack", lib().bsdb_dev_text_pack(*head, *tail))
+        else:
+            _check("bsdb_dev_text_pack_blocked", lib().bsdb_dev_text_pack_blocked(*head, block_size, *tail))
         return {"image": image[: int(runs.sum())], "run_bytes": [int(x) for x in runs], "addr": addr[:count],
                 "blob": blob[: blob_bytes.value], "off": off[: count + 1],
                 "value8": value8[:count] if approximate else None, "value_len": value_len[:count] if approximate else None}
@@ -1021,15 +1037,17 @@ class Context:
         _check("bsdb_text_set_chunk", lib().bsdb_text_set_chunk(self._h, nbytes))
 
     def text_build(self, paths, separator, kv_base: str, partitions: int, width: int, index_path: str,
-                   index_a_path: Optional[str] = None, approximate: bool = False):
-        """bsdb_text_build: (Mph, report dict).  A failure raises BsdbError
-        with the report so far in ``.text_report``."""
+                   index_a_path: Optional[str] = None, approximate: bool = False, fmt: int = 0, block_size: int = 4096):
+        """bsdb_text_build_layout: (Mph, report dict); fmt 0 the compact kv.db
+        layout (bsdb_text_build), 1 the blocked one in blocks of `block_size`
+        bytes.  A failure raises BsdbError with the report so far in
+        ``.text_report``."""
         arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
         report = (C.c_uint64 * TEXT_WORDS)()
         h = C.c_void_p()
-        rc = lib().bsdb_text_build(self._h, arr, len(paths), self._sep(separator), os.fsencode(kv_base), partitions,
-                                   width, 1 if approximate else 0, os.fsencode(index_path),
-                                   os.fsencode(index_a_path) if index_a_path else None, report, C.byref(h))
+        rc = lib().bsdb_text_build_layout(self._h, arr, len(paths), self._sep(separator), os.fsencode(kv_base), partitions,
+                                          fmt, block_size, width, 1 if approximate else 0, os.fsencode(index_path),
+                                          os.fsencode(index_a_path) if index_a_path else None, report, C.byref(h))
         rep = {k: int(v) for k, v in zip(TEXT_FIELDS, report)}
         if rc != BSDB_OK:
             e = BsdbError("bsdb_text_build", rc)

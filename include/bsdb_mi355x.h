@@ -878,6 +878,47 @@ int bsdb_dev_db_gather(bsdb_db *db, const uint64_t *d_src, const uint64_t *d_vof
  *   takes lines of any length).  BSDB_EDUP comes back as from any build: the
  *   kv.db files are complete then, so bsdb_kv_find_duplicates names the records.
  *   The empty input builds the empty database.
+ *
+ * THE BLOCKED LAYOUT (format 1; what the reference's Builder writes without
+ * -c: SimpleBlockedKVWriter with 4096-byte blocks, BlockedKVWriter.java:45-74,
+ * :134-136).  The placement rule, for one run (the records the partition rule
+ * gives partition p in one chunk, in input order), a block size B and the size
+ * F of kv.db.<p> before the run; size = 3 + kLen + vLen:
+ *   small    (size <= B)  if a block is open and B - fill < size, the open block
+ *            is closed: appended to the file at its current end.  The record's
+ *            offset in the (then open, or newly opened) block is fill; fill +=
+ *            size.  A record that exactly fills the block leaves it open and
+ *            full; the next small record closes it.
+ *   large    (size > B; text records are at most 32 768 bytes, so only for B <
+ *            32 768)  a block of its own of ceil(size / 4096) x 4096 bytes, at
+ *            offset 0, appended AT ONCE, ahead of the block that is open at that
+ *            moment; that block stays open and keeps filling.
+ *   end      the run's end closes the open block.  DEVIATION 6: the reference's
+ *            open block lives on across puts until finish; here every chunk's
+ *            run ends its block, at most one partial block per partition and
+ *            chunk.  The reference's reader and scan step over such a block like
+ *            any other (BlockedKVWriter.java:90-117).
+ *   bytes    a block's records sit back to back from offset 0, every other byte
+ *            of the block is 0, the end mark after the last record included; a
+ *            record's first byte (kLen >= 1) is never 0.
+ *   address  p << 56 | (block bytes / 4096) << 48 | (block file position / 4096)
+ *            << 16 | offset.
+ *   limits   B a multiple of 4096 in 4096 .. 65 536 (16 bits of offset); F a
+ *            multiple of 4096; no file beyond 2^44 bytes (32 bits of pages);
+ *            else BSDB_EINVAL.
+ * bsdb_text_image_max: an upper bound of a chunk's image (host only): format 0
+ *   1.5 x bytes + 16; format 1 2 x (bytes + bytes / 4 + 2) + partitions x
+ *   block_size + 16.
+ * bsdb_dev_text_pack_blocked: bsdb_dev_text_pack into the blocked layout.
+ *   h_part_size[p] must be a multiple of 4096; h_run_bytes[p] comes back as one:
+ *   run p's image is its file bytes in file order, the runs back to back in
+ *   d_image.  The key blob, its offsets and the value heads are those of
+ *   bsdb_dev_text_pack.  BSDB_EINVAL, with nothing written, when image_cap or
+ *   blob_cap is too small or an argument breaks the limits.
+ * bsdb_text_build_layout: bsdb_text_build with the layout chosen: format 0
+ *   (block_size ignored) is bsdb_text_build itself, format 1 writes blocked
+ *   kv.db files that bsdb_kv_scan / bsdb_kv_verify_index / bsdb_db_open read
+ *   with format = 1 and the same block_size.
  * ------------------------------------------------------------------------- */
 #define BSDB_TEXT_WORDS 10
 uint64_t bsdb_text_max_records(uint64_t bytes);
@@ -895,6 +936,17 @@ int bsdb_text_set_chunk(bsdb_ctx *ctx, uint64_t bytes);
 int bsdb_text_build(bsdb_ctx *ctx, const char *const *paths, int nfiles, int separator, const char *kv_base,
                     int partitions, uint32_t width, int approximate, const char *index_path, const char *index_a_path,
                     uint64_t *report /* BSDB_TEXT_WORDS */, bsdb_mph **out);
+uint64_t bsdb_text_image_max(uint64_t bytes, int partitions, int format, uint32_t block_size);
+int bsdb_dev_text_pack_blocked(bsdb_ctx *ctx, const uint8_t *d_text, uint64_t bytes, const uint32_t *d_kpos,
+                               const uint32_t *d_klen, const uint32_t *d_vpos, const uint32_t *d_vlen, uint64_t count,
+                               int partitions, uint32_t block_size, const uint64_t *h_part_size, uint8_t *d_image,
+                               uint64_t image_cap, uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob,
+                               uint64_t blob_cap, uint64_t *d_off, uint64_t *h_blob_bytes, uint64_t *d_value8,
+                               uint8_t *d_value_len, void *stream);
+int bsdb_text_build_layout(bsdb_ctx *ctx, const char *const *paths, int nfiles, int separator, const char *kv_base,
+                           int partitions, int format, uint32_t block_size, uint32_t width, int approximate,
+                           const char *index_path, const char *index_a_path, uint64_t *report /* BSDB_TEXT_WORDS */,
+                           bsdb_mph **out);
 
 #ifdef __cplusplus
 }

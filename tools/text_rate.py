@@ -14,6 +14,14 @@ sha256.  Medians of 5 timed runs after 2 warm-ups, all values kept.
   (c) the solve   split + pack kernel time of the whole set beside the GOV
                   build (hash + solve, device events) of the same keys
 
+  --blocked       a leg of its own (default output profiles/text/
+                  c2_blocked.json): per chunk, the device-event time of split +
+                  blocked pack (bsdb_dev_text_pack_blocked, --block-size) beside
+                  split + compact pack of the same chunk in the same run, their
+                  ratio, and the blocked image's bytes against the compact
+                  image's.  With --once every leg runs once and nothing is
+                  written: the form to put under a kernel trace.
+
 The lines are generated on the host.  --lines defaults to 1e7: generating 1e8
 lines (5 GB of text) on the host and building them seven times takes minutes;
 pass --lines 100000000 for the full C2 size.
@@ -63,13 +71,67 @@ def timed(fn):
     return {"median": statistics.median(vals), "values": vals}
 
 
+def blocked_leg(ctx, torch, text, cuts, a) -> dict:
+    """Split + pack per chunk, compact and blocked, device events around each pair of calls."""
+    from bsdb_amd.native import text_image_max
+
+    def ev_ms(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / 1e3
+
+    chunks = []
+    for lo, hi in cuts:
+        n = hi - lo
+        t = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+        t[:n] = torch.from_numpy(text[lo:hi]).cuda()
+        desc = torch.empty((4, n // 4 + 1), dtype=torch.int32, device="cuda")
+        image = torch.empty(text_image_max(n, a.partitions, 1, a.block_size), dtype=torch.uint8, device="cuda")
+        blob = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+        state = {}
+
+        def leg(block_size):
+            _, rep = ctx.text_split(t, " ", nbytes=n, desc=desc)
+            k = int(rep[1])
+            out = ctx.text_pack(t, desc, k, a.partitions, [0] * a.partitions, nbytes=n, image=image, blob=blob,
+                                block_size=block_size)
+            state[block_size] = (k, sum(out["run_bytes"]))
+
+        if a.once:
+            leg(None)
+            leg(a.block_size)
+            torch.cuda.synchronize()
+            continue
+        compact = timed(lambda: ev_ms(lambda: leg(None)))
+        blocked = timed(lambda: ev_ms(lambda: leg(a.block_size)))
+        chunks.append({"bytes": n, "records": state[None][0], "compact_split_pack_s": compact,
+                       "blocked_split_pack_s": blocked, "ratio": blocked["median"] / compact["median"],
+                       "compact_image_bytes": state[None][1], "blocked_image_bytes": state[a.block_size][1],
+                       "image_ratio": state[a.block_size][1] / state[None][1]})
+        del t, desc, image, blob
+    if a.once:
+        return {}
+    tot_c = sum(c["compact_split_pack_s"]["median"] for c in chunks)
+    tot_b = sum(c["blocked_split_pack_s"]["median"] for c in chunks)
+    return {"block_size": a.block_size, "chunks": chunks, "compact_total_s": tot_c, "blocked_total_s": tot_b,
+            "ratio": tot_b / tot_c,
+            "image_ratio": sum(c["blocked_image_bytes"] for c in chunks) / sum(c["compact_image_bytes"] for c in chunks)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lines", type=int, default=10_000_000)
     ap.add_argument("--partitions", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "text", "c2.json"))
+    ap.add_argument("--out", default=None, help="default profiles/text/c2.json, with --blocked c2_blocked.json")
+    ap.add_argument("--blocked", action="store_true", help="only the blocked leg beside the compact one")
+    ap.add_argument("--block-size", type=int, default=4096)
+    ap.add_argument("--once", action="store_true", help="with --blocked: every leg once, nothing written")
     ap.add_argument("--tmp", default=None, help="directory for the text and the database (default: a temporary one)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "text", "c2_blocked.json" if a.blocked else "c2.json")
     import torch
     from bsdb_amd import Context
     from bsdb_amd.native import LIB_PATH, TEXT_FIELDS
@@ -92,6 +154,20 @@ def main():
             hi = lo + int(np.flatnonzero(text[lo:hi] == 10)[-1]) + 1
         cuts.append((lo, hi))
         lo = hi
+    if a.blocked:
+        with Context(0) as ctx:
+            res["blocked"] = blocked_leg(ctx, torch, text, cuts, a)
+        if not a.tmp:
+            shutil.rmtree(tmp, ignore_errors=True)
+        if not a.once:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+            print(json.dumps({"lines": a.lines, "text_bytes": res["text_bytes"], "blocked_over_compact": res["blocked"]["ratio"],
+                              "compact_s": res["blocked"]["compact_total_s"], "blocked_s": res["blocked"]["blocked_total_s"],
+                              "image_ratio": res["blocked"]["image_ratio"]}))
+        return
     with Context(0) as ctx:
         def ev_ms(fn):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
