@@ -77,6 +77,27 @@ __device__ __forceinline__ uint4 ntload16(const void *p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// Inclusive scan of x over the 64 lanes of a wave with `op` (associative, 0 its
+// neutral element: add or max of unsigned), on the VALU's DPP lane shifts, no
+// LDS: four steps inside each row of 16 lanes (row_shr 1, 2, 4, 8; a lane whose
+// source falls outside its row takes 0), then lane 15 of each row into rows 1
+// and 3 (row_bcast:15) and lane 31 into rows 2 and 3 (row_bcast:31).  Every
+// lane of the wave must be active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_or_0(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xf, false);
+}
+template <class Op>
+__device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t x, Op op) {
+    x = op(x, dpp_or_0<0x111, 0xf>(x));
+    x = op(x, dpp_or_0<0x112, 0xf>(x));
+    x = op(x, dpp_or_0<0x114, 0xf>(x));
+    x = op(x, dpp_or_0<0x118, 0xf>(x));
+    x = op(x, dpp_or_0<0x142, 0xa>(x));
+    x = op(x, dpp_or_0<0x143, 0xc>(x));
+    return x;
+}
+
 // Bounds-checked little-endian u64 read from global memory: dword loads in the
 // body, byte loads for the ragged last dword of the blob (never past `limit`).
 __device__ __forceinline__ uint32_t gload32(const uint8_t *base, uint64_t limit, uint64_t a) {
@@ -558,27 +579,38 @@ __global__ __launch_bounds__(NT, 4) void k_pass1_d13(P1Args a, uint64_t ntiles) 
 // a 16-byte write-out.  One 1024-thread workgroup per CU, 16384-key tiles,
 // ONE barrier per tile.
 //  * Hash: a key's 2-byte partition-local id goes from the hash straight into
-//    its partition's LDS bin (rank = the bin counter's old value); no bucket
-//    id or rank is held in registers, so the four quarters of a tile live in
-//    four register sets and the next tile's quarter q is loaded as soon as
-//    this tile's quarter q is hashed (three quarters of prefetch).
+//    its partition's LDS bin; no bucket id or rank is held in registers, so
+//    the four quarters of a tile live in four register sets and the next
+//    tile's quarter q is loaded as soon as this tile's quarter q is hashed
+//    (three quarters of prefetch).
+//  * Insert: a bin's counter holds the LDS byte offset of the bin's next free
+//    slot, so the rank atomic (ds_add_rtn_u32, + 2) returns where the id
+//    goes: per key a shift (bin), a shift (counter address), one clamp to the
+//    buffer's last slot and the id's mask, then ds_write_b16.  The tile loop
+//    runs two tiles per iteration, one per bin buffer, so each half knows
+//    its buffer at compile time.
 //  * Bins are double-buffered.  After the tile's barrier the owner lane of
-//    partition p (lane p/16 of wave p%16) takes its count c and reserves the
-//    bin's whole 8-id chunks (c & ~7) in the XCD-shared region of copy t % 8
-//    with one cursor atomic; runs therefore start 16-byte aligned.  The
-//    remainder (c & 7 ids) is not padded: the owner moves it to the start of
-//    the same bin once its chunks are out (during the next tile) and re-arms
-//    the counter at it, so the tile after next ranks on top of it.  Only the
-//    workgroup's last two remainders per partition are padded (0xFFFF, which
-//    pass 2 adds as 0), in one run at the end: pads fell from ~6 % of the
-//    ids to ~0.1 %.
-//  * During the next tile the wave streams its partitions' bins out as
-//    16-byte chunks (ds_read_b128 -> global_store_dwordx4), chunks of all its
-//    partitions packed across lanes: ~3 store instructions per wave per tile
-//    instead of one 2-byte store per id.
-// A bin holds 128 ids (tile share 61 +- 8); a run that would not fit padded
-// (c > 120) or a full region raises the overflow flag and the chunk is
-// recounted with direct atomics.
+//    bin p (lane p % PPW of wave p / PPW) takes its count c = (counter - the
+//    bin's first slot) / 2 and reserves the bin's whole 8-id chunks (c & ~7)
+//    in the XCD-shared region of copy t % 8 with one cursor atomic; runs
+//    therefore start 16-byte aligned.  The remainder (c & 7 ids) is not
+//    padded: the owner moves it to the start of the same bin once its chunks
+//    are out (during the next tile) and re-arms the counter behind it, so the
+//    tile after next ranks on top of it.  Only the workgroup's last two
+//    remainders per bin are padded (0xFFFF, which pass 2 adds as 0), in one
+//    run at the end: pads fell from ~6 % of the ids to ~0.1 %.
+//  * During the next tile the wave streams its bins out as 16-byte chunks
+//    (ds_read_b128 -> global_store_dwordx4), chunks of all its bins packed
+//    across lanes: ~3 store instructions per wave per tile instead of one
+//    2-byte store per id.  Which owner a chunk belongs to comes from a
+//    running maximum over the lanes (DPP) of the owners' start marks, and the
+//    chunk's addresses from a per-wave table the owners publish once per
+//    tile: 1 + 3 per round LDS instructions and two dependent LDS waits per
+//    round, where a binary search over the owners with ds_bpermute took 6 + 7
+//    per round and six waits (write_out).
+// A bin holds CAPB ids (the host plan's: 136 of the 269 bins at C4, tile
+// share 61 +- 8); a bin that receives more, or a full region, raises the
+// overflow flag and the span is recounted with direct atomics.
 constexpr int D13E_NW = D13E_NT / 64;
 constexpr uint16_t ID_PAD = 0xFFFF;                       // not a local id (ids are < 2^15)
 
@@ -599,6 +631,13 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     constexpr int NT = D13E_NT, NW = D13E_NW, TILE = D13E_TILE;
     __shared__ __align__(16) uint16_t bins[2][D13E_BIN_IDS];
     __shared__ uint32_t cnt[2][D13E_MAXP];
+    // the write-out's map: per wave, the owner (tagged, see write_out) whose
+    // run starts at each of a round's 64 chunks, and per owner the source and
+    // destination offsets of its chunk 0 less 8 * its first chunk
+    constexpr int MAXPPW = (D13E_MAXP + D13E_NW - 1) / D13E_NW;
+    static_assert(MAXPPW < 31, "owner index + 1 in 5 bits");
+    __shared__ uint32_t wo_start[D13E_NW][64];
+    __shared__ uint2 wo_own[D13E_NW][MAXPPW];
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const uint32_t P = a.nparts;  // bins: bucket >> bin_shift
@@ -606,7 +645,15 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     const uint32_t bsh = a.bin_shift;
     const uint32_t mult = (uint32_t)a.multiplier;
     const uint64_t G = gridDim.x;
-    for (int i = tid; i < 2 * D13E_MAXP; i += NT) (&cnt[0][0])[i] = 0;
+    // bin p's counter of buffer c holds the byte offset, from bins[0][0], of
+    // the bin's next free slot (not the bin's fill); an empty bin's:
+    auto bin_off = [&](uint32_t c, uint32_t p) { return (c * (uint32_t)D13E_BIN_IDS + p * CAPB) * 2u; };
+    for (int i = tid; i < 2 * D13E_MAXP; i += NT) {
+        const uint32_t c = i >= D13E_MAXP, p = i - c * D13E_MAXP;
+        cnt[c][p] = p < P ? bin_off(c, p) : 0u;
+    }
+    static_assert(NT == D13E_NW * 64, "one thread per wo_start word");
+    (&wo_start[0][0])[tid] = 0;
     const uint64_t t0 = blockIdx.x;
     if (t0 >= ntiles) return;
     // wave w owns the contiguous partitions [w*PPW, w*PPW + PPW): lane l < PPW
@@ -656,7 +703,7 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     bool ovf = false;
     // the quarter's D13_Q keys hashed first, then their rank atomics issued
     // together and their ids stored: one LDS round trip per quarter
-    auto hash_q = [&](int q, uint32_t cur) {
+    auto hash_q = [&](int q, uint32_t cur) __attribute__((always_inline)) {
         uint32_t b[D13_Q], r[D13_Q];
 #pragma unroll
         for (int j = 0; j < D13_Q; ++j) {
@@ -666,19 +713,28 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
                 b[j] = spooky_fix_bucket<L>(S[q][j].x, S[q][j].y, S[q][j].z, S[q][j].w, seed, mult);
         }
 #pragma unroll
-        for (int j = 0; j < D13_Q; ++j) r[j] = atomicAdd(&cnt[cur][b[j] >> bsh], 1u);
+        for (int j = 0; j < D13_Q; ++j) r[j] = atomicAdd(&cnt[cur][b[j] >> bsh], 2u);
+        // The rank atomic's return is the slot's byte offset.  ONE clamp, to
+        // the last slot of bins[cur]: an id past its bin's CAPB slots lands
+        // in a later bin of the same buffer (or on the buffer's last slot),
+        // never outside bins[cur].  Such a stray id is never counted: a bin's
+        // counter passes its last slot only if its owner then reads c > CAPB
+        // and raises the overflow flag, pass 2 skips the whole span of a
+        // raised flag (k_pass2b returns on it), and the span is recounted
+        // from the keys (k_overflow_fallback).  The bins a stray id can spoil
+        // -- this tile's, and through a carried remainder those of later
+        // tiles of this launch -- all belong to that span.
+        const uint32_t last = (cur * (uint32_t)D13E_BIN_IDS + (uint32_t)D13E_BIN_IDS - 1u) * 2u;
 #pragma unroll
-        for (int j = 0; j < D13_Q; ++j) {
-            // branch-free: an overflowing bin (flagged below) reuses its last slot
-            const uint32_t slot = __umul24(b[j] >> bsh, CAPB) + min(r[j], CAPB - 1u);  // (v_mad_u32_u24 + v_min)
-            __builtin_assume(slot < (uint32_t)D13E_BIN_IDS);
-            bins[cur][slot] = (uint16_t)(b[j] & (PART_BUCKETS - 1));
-        }
+        for (int j = 0; j < D13_Q; ++j)
+            *reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(&bins[0][0]) + min(r[j], last)) =
+                (uint16_t)(b[j] & (PART_BUCKETS - 1));
     };
     // owner state of the previous tile: whole-chunk count, remainder and
     // cursor base of my_p
     uint32_t c8_prev = 0, rm_prev = 0, b_prev = 0, copy_prev = 0;
-    auto write_out = [&](uint32_t prev) {
+    uint32_t wo_tag = 0;  // rounds of write_out so far, times 32
+    auto write_out = [&](uint32_t prev) __attribute__((always_inline)) {
         // chunks (8 ids) of this wave's partitions, packed across lanes:
         // owner lane j covers chunk indices [st_j, st_j + nch_j)
         // b_prev is first touched here, a whole tile after its atomic (a use
@@ -686,30 +742,43 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         const bool fits = (uint64_t)b_prev + c8_prev <= a.cap;
         ovf |= my_p < P && !fits;
         const uint32_t nch = (my_p < P && fits) ? c8_prev / 8 : 0;
-        uint32_t x = nch;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (l >= d) x += y;
-        }
+        const uint32_t x = wave_scan_dpp(nch, [](uint32_t p, uint32_t q) { return p + q; });
         const uint32_t st = x - nch;
         const uint32_t total = __builtin_amdgcn_readlane(x, 63);
         uint16_t *const rbase = a.ids + (uint64_t)copy_prev * P * a.cap;  // P*cap < 2^32 (host plan)
+        // The chunk-to-owner map without a search.  Owner j publishes, once,
+        // where its chunk 0 is read and written, less 8 * st_j, so chunk i of
+        // the wave is at those offsets plus 8 * i.  Per round of 64 chunks,
+        // the owners whose run starts in the round (and is not empty: starts
+        // are then distinct) store tag + j + 1 at their first chunk's lane in
+        // wo_start; a running maximum over the lanes (DPP, no LDS) then gives
+        // every chunk the last owner that started at or before it.  tag = 32
+        // * (rounds so far + 1) grows with every round, so what earlier
+        // rounds left in wo_start is smaller than the carry -- tag + the
+        // owner of the previous round's last chunk -- and loses the maximum:
+        // the table is zeroed once per launch, not per round.  (2^27 rounds
+        // before the tag wraps: over 10^11 keys per workgroup, and a launch
+        // has at most 2^32.)
+        if ((uint32_t)l < PPW)
+            wo_own[w][l] = make_uint2(my_p * CAPB - 8u * st, (uint32_t)((uint64_t)my_p * a.cap) + b_prev - 8u * st);
+        uint32_t carry = 0;  // owner + 1 of the previous round's last chunk
         for (uint32_t i0 = 0; i0 < total; i0 += 64) {
+            wo_tag += 32;
+            if (nch && st - i0 < 64u) wo_start[w][st - i0] = wo_tag + l + 1;
+            uint32_t v = max(wo_start[w][l], wo_tag + carry);
+            v = wave_scan_dpp(v, [](uint32_t p, uint32_t q) { return max(p, q); });
+            carry = __builtin_amdgcn_readlane(v, 63) & 31u;
+            // (chunk 0 of a tile with total > 0 is some owner's first: j + 1
+            // >= 1 wherever i < total; the min keeps a lane past total inside
+            // the table)
+            const uint32_t j = min((v & 31u) - 1u, (uint32_t)MAXPPW - 1u);
+            const uint2 o = wo_own[w][j];
             const uint32_t i = i0 + l;
-            // owner lane j = last lane (of the first 32) with st_j <= i
-            int j = 0;
-#pragma unroll
-            for (int step = 16; step >= 1; step >>= 1) {
-                const uint32_t s_try = __shfl(st, j + step, 64);
-                if (s_try <= i) j += step;
-            }
-            const uint32_t bj = __shfl(b_prev, j, 64), sj = __shfl(st, j, 64);
-            const uint32_t k = i - sj;
-            const uint32_t p = (uint32_t)w * PPW + j;
             if (i < total) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(&bins[prev][p * CAPB + 8 * k]);
-                *reinterpret_cast<uint4 *>(rbase + (uint64_t)p * a.cap + bj + 8 * k) = v;
+                // (32-bit sums: a chunk's ids lie inside bins[prev], and its
+                // destination inside the copy's P * cap ids)
+                const uint4 v16 = *reinterpret_cast<const uint4 *>(&bins[prev][o.x + 8 * i]);
+                *reinterpret_cast<uint4 *>(rbase + (uint64_t)(o.y + 8 * i)) = v16;
             }
         }
         // the remainder to the bin's start, for the tile after next (after
@@ -733,7 +802,7 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     __syncthreads();  // cnt zeroed
     uint32_t cur = 0;
     bool have_prev = false;
-    for (uint64_t t = t0; t < ntiles; t += G, cur ^= 1) {
+    auto tile = [&](const uint32_t cur, const uint64_t t) __attribute__((always_inline)) {
         hash_q(0, cur);
         load_q(0, t + G);
         hash_q(1, cur);
@@ -750,12 +819,13 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
         rm_prev = 0;
         b_prev = 0;
         if (my_p < P) {
-            const uint32_t c = cnt[cur][my_p];
+            const uint32_t base = bin_off(cur, my_p);
+            const uint32_t c = (cnt[cur][my_p] - base) / 2u;  // the carried remainder included
             ovf |= c > CAPB;
             const uint32_t cc = c > CAPB ? 0 : c;  // (an overflow is recounted: nothing kept)
             c8_prev = cc & ~7u;
             rm_prev = cc & 7u;
-            cnt[cur][my_p] = rm_prev;  // the tile after next ranks after the carried ids
+            cnt[cur][my_p] = base + 2u * rm_prev;  // the tile after next ranks after the carried ids
         }
         // Every lane issues the atomic -- a lane without a partition adds 0
         // to a word of this workgroup's own scratch -- so the instruction is
@@ -771,6 +841,21 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
                                c8_prev);
         copy_prev = copy;
         have_prev = true;
+    };
+    // Two tiles per iteration, so each half knows its bin buffer at compile
+    // time; an odd tile count leaves after the first half.  cur: the buffer
+    // the next tile would fill.  (The halves' VALU count is that of the
+    // one-tile loop -- the clamp becomes a literal, the counters' base stays a
+    // register, cnt lying past the 64 KiB an LDS offset field reaches -- yet
+    // pass 1 at C4 ran 0.65 ms faster on top of the insert and the map; why
+    // is not established.  DESIGN §4.1.)
+    for (uint64_t t = t0; t < ntiles; t += G) {
+        tile(0u, t);
+        cur = 1;
+        t += G;
+        if (t >= ntiles) break;
+        tile(1u, t);
+        cur = 0;
     }
     if (have_prev) write_out(cur ^ 1);
     // the last two remainders of my_p: the one carried to the start of
@@ -778,7 +863,8 @@ __global__ __launch_bounds__(D13E_NT, 1) void k_pass1_d13e(P1Args a, uint64_t nt
     // by write_out to the start of bins[cur ^ 1]: one run padded to 8
     if (have_prev && my_p < P) {
         uint16_t *const bc = &bins[cur][my_p * CAPB];
-        const uint32_t r0 = cnt[cur][my_p], r1 = rm_prev;  // (<= 7 each)
+        const uint32_t r0 = (cnt[cur][my_p] - bin_off(cur, my_p)) / 2u;
+        const uint32_t r1 = rm_prev;  // (<= 7 each)
         for (uint32_t e = 0; e < r1; ++e) bc[r0 + e] = bins[cur ^ 1][my_p * CAPB + e];
         const uint32_t c8 = (r0 + r1 + 7) & ~7u;
         for (uint32_t e = r0 + r1; e < c8; ++e) bc[e] = ID_PAD;

@@ -175,6 +175,12 @@ __device__ __forceinline__ void short_end_w(W64 &h0, W64 &h1, W64 &h2, W64 &h3) 
 // Same arithmetic with the adds as one v_lshl_add_u64 (measured on gfx950:
 // one issue slot, the same rate as a 32-bit op, where v_add_co + v_addc take
 // two); xors and rotates stay on the 32-bit halves.
+// (Inline asm, not `a + b`: the compiler selects the same instruction for the
+// plain add, but then re-associates the hash's adds -- 13-byte keys: 2 more
+// v_lshl_add_u64 and 2 more v_mov_b32 per key, 1 129 -> 1 209 VALU per
+// 16-key loop -- and pass 1 at C4 ran 0.68 ms slower.  The asm form's price is
+// the `s_nop 0` the compiler puts after it where the next instruction reads
+// the sum, 35 of them per loop, which other waves fill.  DESIGN §4.1.)
 __device__ __forceinline__ uint64_t add_u(uint64_t a, uint64_t b) {
     uint64_t r;
     asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(b));

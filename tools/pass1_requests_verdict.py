@@ -25,7 +25,9 @@ def main():
     out = {}
     # profiles/pass1_requests/: req_a, req_b, req_c; profiles/pass2_span/: span_a, span_ab, span_c, final
     # profiles/launch_length/: final (the default launch length), chunk_2p<k> (bench.py --chunk 2^k)
-    names = ["parent", "req_a", "req_b", "req_c", "span_a", "span_ab", "span_c", "all", "final"]
+    # profiles/pass1_insert/: ins_slot, ins_map, ins_add64, ins_slot_map, ins_slot_cur_map, all, final
+    names = ["parent", "req_a", "req_b", "req_c", "span_a", "span_ab", "span_c",
+             "ins_slot", "ins_map", "ins_add64", "ins_slot_map", "ins_slot_cur_map", "all", "final"]
     names += sorted(f[:-6] for f in os.listdir(d) if f.startswith("chunk_2p") and f.endswith(".jsonl"))
     for name in names:
         path = os.path.join(d, name + ".jsonl")
