@@ -60,7 +60,7 @@ void get_gather_launch(bsdb_ctx *c, const bsdb_db *db, const uint64_t *d_src, co
     a.values = d_values;
     a.value_bytes = value_bytes;
     const uint32_t mis = (uint32_t)((uintptr_t)d_values & 15);
-    k_get_gather<<<get_gather_grid(value_bytes, mis, c->num_cus), 256, 0, s>>>(a);
+    k_get_gather<<<piece_grid(value_bytes, mis, c->num_cus), 256, 0, s>>>(a);
 }
 
 // Releases a db's device memory on its own device (its context may be gone).

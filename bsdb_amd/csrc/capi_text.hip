@@ -66,156 +66,183 @@ struct TextDesc {
     const uint32_t *kpos, *klen, *vpos, *vlen;
 };
 
-// The pack of one chunk's `count` records; the caller holds the context's lock
-// and has set the device.  Waits for the scans (the sizes go back to the
-// host, and nothing is written before they are known to fit).
-int text_pack_impl(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const TextDesc &d, uint64_t count, int partitions,
-                   const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap, uint64_t *h_run_bytes,
-                   uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off, uint64_t *h_blob_bytes,
-                   uint64_t *d_value8, uint8_t *d_value_len, hipStream_t s) {
-    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = 0;
-    if (h_blob_bytes) *h_blob_bytes = 0;
-    if (!count) {
-        if (d_off) HIP_OK(hipMemsetAsync(d_off, 0, 8, s));
-        return BSDB_OK;
-    }
-    int rc;
-    if ((rc = c->t_size.grow(2 * 4 * count)) || (rc = c->t_roff.grow(8 * (count + 1)))) return rc;
-    uint32_t *rsize = c->t_size.as<uint32_t>(), *ksize = rsize + count;
-    uint64_t *roff = c->t_roff.as<uint64_t>();
-    const uint32_t lgrid = text_lane_grid(count, c->num_cus);
-    k_text_sizes<<<lgrid, 256, 0, s>>>(d.klen, d.vlen, count, rsize, ksize);
-    if ((rc = text_scan(c, rsize, count, roff, s))) return rc;
-    if (d_off && (rc = text_scan(c, ksize, count, d_off, s))) return rc;
+// What a pack reads and writes: bsdb_dev_text_pack(_blocked)'s arguments.
+struct TextPackIO {
+    const uint8_t *d_text;
+    uint64_t bytes;
+    TextDesc d;
+    uint64_t count;
+    int partitions;
+    uint32_t B;  // the blocked layout's block bytes; 0: the compact layout
+    const uint64_t *h_part_size;
+    uint8_t *d_image;
+    uint64_t image_cap, *h_run_bytes, *d_addr;
+    uint8_t *d_blob;
+    uint64_t blob_cap, *d_off, *h_blob_bytes, *d_value8;
+    uint8_t *d_value_len;
+};
+
+bool text_pack_bad_args(const bsdb_ctx *c, const TextPackIO &io) {
+    const TextDesc &d = io.d;
+    return !c || io.bytes > TEXT_MAX_BYTES || (io.bytes && !io.d_text) || !aligned16(io.d_text) ||
+           io.count > text_max_records(io.bytes) || io.partitions < 1 || io.partitions > TEXT_MAX_PARTS || !io.h_part_size ||
+           !io.h_run_bytes || (io.count && (!d.kpos || !d.klen || !d.vpos || !d.vlen)) ||
+           (((uintptr_t)d.kpos | (uintptr_t)d.klen | (uintptr_t)d.vpos | (uintptr_t)d.vlen) & 3) || (!io.d_blob != !io.d_off) ||
+           (!io.d_value8 != !io.d_value_len) || (((uintptr_t)io.d_addr | (uintptr_t)io.d_off | (uintptr_t)io.d_value8) & 7);
+}
+
+// A pack under way: what text_pack_impl hands to the layout's placement and
+// what the placement finds out.
+struct TextPlacing {
     TextRuns runs{};
-    runs.partitions = (uint32_t)partitions;
-    uint64_t at[TEXT_MAX_PARTS + 1] = {}, blob_bytes = 0;
-    for (int p = 0; p <= partitions; ++p) {
-        runs.bound[p] = text_run_bound(count, (uint32_t)partitions, (uint32_t)p);
-        HIP_OK(hipMemcpyAsync(&at[p], roff + runs.bound[p], 8, hipMemcpyDeviceToHost, s));
-    }
-    if (d_off) HIP_OK(hipMemcpyAsync(&blob_bytes, d_off + count, 8, hipMemcpyDeviceToHost, s));
+    TextPack pack{};                 // the chunk and its records; dst / off per launch
+    uint32_t *rsize, *ksize;         // [count] the records' bytes in the image and in the key blob
+    uint32_t lgrid;                  // a record per lane
+    const uint64_t *roff = nullptr;  // compact: the scan of rsize, the addresses' offsets
+    uint64_t blob_bytes = 0;
+    uint64_t run[TEXT_MAX_PARTS] = {};
+};
+
+// The records' sizes (ssize: the blocked layout's, else null), the layout's
+// scan sized -> scan and the key blob's offsets.
+int text_sizes(bsdb_ctx *c, const TextPackIO &io, const TextPlacing &pl, uint32_t *ssize, const uint32_t *sized, uint64_t *scan,
+               hipStream_t s) {
+    k_text_sizes<<<pl.lgrid, 256, 0, s>>>(io.d.klen, io.d.vlen, io.count, io.B, pl.rsize, pl.ksize, ssize);
+    int rc;
+    if ((rc = text_scan(c, sized, io.count, scan, s))) return rc;
+    return io.d_off ? text_scan(c, pl.ksize, io.count, io.d_off, s) : BSDB_OK;
+}
+
+// The placement's one wait: its own read-backs, queued by the caller, and the key blob's size.
+int text_sizes_wait(const TextPackIO &io, TextPlacing &pl, hipStream_t s) {
+    if (io.d_off) HIP_OK(hipMemcpyAsync(&pl.blob_bytes, io.d_off + io.count, 8, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    const uint64_t image_bytes = at[partitions];
-    if ((d_image && image_bytes > image_cap) || (d_blob && blob_bytes > blob_cap)) return BSDB_EINVAL;
-    for (int p = 0; p < partitions; ++p) {
-        const uint64_t run = at[p + 1] - at[p];
-        if (h_part_size[p] > TEXT_MAX_FILE || run > TEXT_MAX_FILE - h_part_size[p]) return BSDB_EINVAL;
-        runs.file_base[p] = h_part_size[p] - at[p];  // (+ roff[r] >= at[p]: the sum never wraps past the file offset)
-    }
-    TextPack a{};
-    a.text = d_text;
-    a.bytes = bytes;
-    a.kpos = d.kpos;
-    a.klen = d.klen;
-    a.vpos = d.vpos;
-    a.vlen = d.vlen;
-    a.count = count;
-    if (d_image) {
-        a.off = roff;
-        a.dst = d_image;
-        a.out_bytes = image_bytes;
-        k_text_pack<true><<<text_pack_grid(image_bytes, (uint32_t)((uintptr_t)d_image & 15), c->num_cus), 256, 0, s>>>(a);
-    }
-    if (d_blob && blob_bytes) {
-        a.off = d_off;
-        a.dst = d_blob;
-        a.out_bytes = blob_bytes;
-        k_text_pack<false><<<text_pack_grid(blob_bytes, (uint32_t)((uintptr_t)d_blob & 15), c->num_cus), 256, 0, s>>>(a);
-    }
-    if (d_addr || d_value8)
-        k_text_outputs<<<lgrid, 256, 0, s>>>(runs, d_text, bytes, d.vpos, d.vlen, roff, count, d_addr, d_value8, d_value_len);
-    if ((rc = launch_status())) return rc;
-    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = at[p + 1] - at[p];
-    if (h_blob_bytes) *h_blob_bytes = blob_bytes;
     return BSDB_OK;
 }
 
-// text_pack_impl for the blocked layout (text_blocked_kernels.hip): blocks of
-// `B` bytes, run p appended to a file of h_part_size[p] bytes (a multiple of
-// 4096).  Waits once, for the placement: the runs' bytes are the events' sums
-// plus the block each run with a small record leaves open at its end.
-int text_pack_blocked_impl(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const TextDesc &d, uint64_t count, int partitions,
-                           uint32_t B, const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap,
-                           uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off,
-                           uint64_t *h_blob_bytes, uint64_t *d_value8, uint8_t *d_value_len, hipStream_t s) {
-    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = 0;
-    if (h_blob_bytes) *h_blob_bytes = 0;
-    if (!count) {
-        if (d_off) HIP_OK(hipMemsetAsync(d_off, 0, 8, s));
-        return BSDB_OK;
-    }
+bool text_pack_too_large(const TextPackIO &io, const TextPlacing &pl, uint64_t image_bytes) {
+    return (io.d_image && image_bytes > io.image_cap) || (io.d_blob && pl.blob_bytes > io.blob_cap);
+}
+
+// k_text_pack of the records `a` names into (dst, out_bytes) by the scan `off`
+template <bool IMAGE>
+void text_pack_launch(bsdb_ctx *c, TextPack a, const uint64_t *off, uint8_t *dst, uint64_t out_bytes, hipStream_t s) {
+    a.off = off, a.dst = dst, a.out_bytes = out_bytes;
+    k_text_pack<IMAGE><<<piece_grid(out_bytes, (uint32_t)((uintptr_t)dst & 15), c->num_cus), 256, 0, s>>>(a);
+}
+
+// The compact layout: a record lies where the scan of the sizes puts it, run p
+// appended to a file of h_part_size[p] bytes.
+int text_place_compact(bsdb_ctx *c, const TextPackIO &io, TextPlacing &pl, hipStream_t s) {
     int rc;
-    if ((rc = c->t_size.grow(2 * 4 * count)) || (rc = c->t_blk.grow(text_place_workspace(count)))) return rc;
-    const uint32_t tiles = (uint32_t)((count + TEXT_TILE - 1) / TEXT_TILE);
-    uint32_t *rsize = c->t_size.as<uint32_t>(), *ksize = rsize + count;
+    if ((rc = c->t_roff.grow(8 * (io.count + 1)))) return rc;
+    uint64_t *roff = c->t_roff.as<uint64_t>();
+    pl.roff = roff;
+    if ((rc = text_sizes(c, io, pl, nullptr, pl.rsize, roff, s))) return rc;
+    uint64_t at[TEXT_MAX_PARTS + 1] = {};
+    for (int p = 0; p <= io.partitions; ++p)
+        HIP_OK(hipMemcpyAsync(&at[p], roff + pl.runs.bound[p], 8, hipMemcpyDeviceToHost, s));
+    if ((rc = text_sizes_wait(io, pl, s))) return rc;
+    const uint64_t image_bytes = at[io.partitions];
+    if (text_pack_too_large(io, pl, image_bytes)) return BSDB_EINVAL;
+    for (int p = 0; p < io.partitions; ++p) {
+        pl.run[p] = at[p + 1] - at[p];
+        if (io.h_part_size[p] > TEXT_MAX_FILE || pl.run[p] > TEXT_MAX_FILE - io.h_part_size[p]) return BSDB_EINVAL;
+        pl.runs.file_base[p] = io.h_part_size[p] - at[p];  // (+ roff[r] >= at[p]: the sum never wraps past the file offset)
+    }
+    if (io.d_image) text_pack_launch<true>(c, pl.pack, roff, io.d_image, image_bytes, s);
+    return BSDB_OK;
+}
+
+// The blocked layout (text_blocked_kernels.hip): blocks of B bytes, run p
+// appended to a file of h_part_size[p] bytes (a multiple of 4096).  The runs'
+// bytes are the events' sums plus the block each run with a small record
+// leaves open at its end.
+int text_place_blocked(bsdb_ctx *c, const TextPackIO &io, TextPlacing &pl, hipStream_t s) {
+    const uint64_t count = io.count;
+    const uint32_t B = io.B, tiles = (uint32_t)((count + TEXT_TILE - 1) / TEXT_TILE);
+    const TextRuns &runs = pl.runs;
+    int rc;
+    if ((rc = c->t_blk.grow(text_place_workspace(count)))) return rc;
     // the workspace, 8-byte arrays first
     uint64_t *S = c->t_blk.as<uint64_t>(), *E = S + count + 1, *PS = E + count + 1, *PL = PS + count + 1;
     uint2 *exl = reinterpret_cast<uint2 *>(PL + count + 1);
     uint32_t *ssize = reinterpret_cast<uint32_t *>(exl + count), *next = ssize + count, *ev = next + count, *boff = ev + count,
              *bend = boff + count, *entry = bend + count, *carry = entry + tiles;
-    const uint32_t lgrid = text_lane_grid(count, c->num_cus);
-    TextRuns runs{};
-    runs.partitions = (uint32_t)partitions;
-    for (int p = 0; p <= partitions; ++p) runs.bound[p] = text_run_bound(count, (uint32_t)partitions, (uint32_t)p);
-    k_blk_sizes<<<lgrid, 256, 0, s>>>(d.klen, d.vlen, count, B, rsize, ksize, ssize);
-    if ((rc = text_scan(c, ssize, count, S, s))) return rc;
-    if (d_off && (rc = text_scan(c, ksize, count, d_off, s))) return rc;
+    if ((rc = text_sizes(c, io, pl, ssize, ssize, S, s))) return rc;
     HIP_OK(hipMemsetAsync(entry, 0, 2 * 4 * (size_t)tiles, s));
     k_blk_tile<<<tiles, 256, 0, s>>>(runs, S, count, B, next, exl);
-    k_blk_chase<<<(uint32_t)partitions, 64, 0, s>>>(runs, exl, count, tiles, entry, carry);
-    k_blk_flags<<<tiles, 256, 0, s>>>(runs, S, rsize, next, entry, carry, count, B, ev, boff, bend);
+    k_blk_chase<<<(uint32_t)io.partitions, 64, 0, s>>>(runs, exl, count, tiles, entry, carry);
+    k_blk_flags<<<tiles, 256, 0, s>>>(runs, S, pl.rsize, next, entry, carry, count, B, ev, boff, bend);
     if ((rc = text_scan(c, ev, count, E, s))) return rc;
-    uint64_t e_at[TEXT_MAX_PARTS + 1] = {}, s_at[TEXT_MAX_PARTS + 1] = {}, blob_bytes = 0;
-    for (int p = 0; p <= partitions; ++p) {
+    uint64_t e_at[TEXT_MAX_PARTS + 1] = {}, s_at[TEXT_MAX_PARTS + 1] = {};
+    for (int p = 0; p <= io.partitions; ++p) {
         HIP_OK(hipMemcpyAsync(&e_at[p], E + runs.bound[p], 8, hipMemcpyDeviceToHost, s));
         HIP_OK(hipMemcpyAsync(&s_at[p], S + runs.bound[p], 8, hipMemcpyDeviceToHost, s));
     }
-    if (d_off) HIP_OK(hipMemcpyAsync(&blob_bytes, d_off + count, 8, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
+    if ((rc = text_sizes_wait(io, pl, s))) return rc;
     TextBlockedRuns br{};
-    uint64_t run[TEXT_MAX_PARTS] = {}, image_bytes = 0;
-    for (int p = 0; p < partitions; ++p) {
-        run[p] = e_at[p + 1] - e_at[p] + (s_at[p + 1] > s_at[p] ? B : 0);
-        if (h_part_size[p] > TEXT_MAX_FILE_BLOCKED || run[p] > TEXT_MAX_FILE_BLOCKED - h_part_size[p]) return BSDB_EINVAL;
+    uint64_t image_bytes = 0;
+    for (int p = 0; p < io.partitions; ++p) {
+        pl.run[p] = e_at[p + 1] - e_at[p] + (s_at[p + 1] > s_at[p] ? B : 0);
+        if (io.h_part_size[p] > TEXT_MAX_FILE_BLOCKED || pl.run[p] > TEXT_MAX_FILE_BLOCKED - io.h_part_size[p]) return BSDB_EINVAL;
         br.image_base[p] = image_bytes;
-        br.file_size[p] = h_part_size[p];
-        image_bytes += run[p];
+        br.file_size[p] = io.h_part_size[p];
+        image_bytes += pl.run[p];
     }
-    if ((d_image && image_bytes > image_cap) || (d_blob && blob_bytes > blob_cap)) return BSDB_EINVAL;
-    if (d_image || d_addr)
-        k_blk_place<<<text_lane_grid(count + 1, c->num_cus), 256, 0, s>>>(runs, br, E, rsize, boff, bend, count, B, image_bytes,
-                                                                           PS, PL, d_addr);
-    TextPack a{};
-    a.text = d_text;
-    a.bytes = bytes;
-    a.kpos = d.kpos;
-    a.klen = d.klen;
-    a.vpos = d.vpos;
-    a.vlen = d.vlen;
-    a.count = count;
-    if (d_image && image_bytes) {
-        TextPackBlocked b{};
-        b.t = a;
-        b.t.dst = d_image;
+    if (text_pack_too_large(io, pl, image_bytes)) return BSDB_EINVAL;
+    if (io.d_image || io.d_addr)
+        k_blk_place<<<text_lane_grid(count + 1, c->num_cus), 256, 0, s>>>(runs, br, E, pl.rsize, boff, bend, count, B, image_bytes, PS,
+                                                                           PL, io.d_addr);
+    if (io.d_image && image_bytes) {
+        TextPackBlocked b{pl.pack, PS, PL, B};
+        b.t.dst = io.d_image;
         b.t.out_bytes = image_bytes;
-        b.PS = PS;
-        b.PL = PL;
-        b.B = B;
-        k_text_pack_blocked<<<text_pack_grid(image_bytes, (uint32_t)((uintptr_t)d_image & 15), c->num_cus), 256, 0, s>>>(b);
+        k_text_pack_blocked<<<piece_grid(image_bytes, (uint32_t)((uintptr_t)io.d_image & 15), c->num_cus), 256, 0, s>>>(b);
     }
-    if (d_blob && blob_bytes) {
-        a.off = d_off;
-        a.dst = d_blob;
-        a.out_bytes = blob_bytes;
-        k_text_pack<false><<<text_pack_grid(blob_bytes, (uint32_t)((uintptr_t)d_blob & 15), c->num_cus), 256, 0, s>>>(a);
-    }
-    if (d_value8)
-        k_text_outputs<<<lgrid, 256, 0, s>>>(runs, d_text, bytes, d.vpos, d.vlen, nullptr, count, nullptr, d_value8, d_value_len);
-    if ((rc = launch_status())) return rc;
-    for (int p = 0; p < partitions; ++p) h_run_bytes[p] = run[p];
-    if (h_blob_bytes) *h_blob_bytes = blob_bytes;
     return BSDB_OK;
+}
+
+// The pack of one chunk's `count` records; the caller holds the context's lock
+// and has set the device.  The layout's placement waits once, for the sizes
+// (they go back to the host, and nothing is written before they are known to
+// fit) and launches the image's kernel; the key blob and the value heads
+// follow it.
+int text_pack_impl(bsdb_ctx *c, const TextPackIO &io, hipStream_t s) {
+    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = 0;
+    if (io.h_blob_bytes) *io.h_blob_bytes = 0;
+    if (!io.count) {
+        if (io.d_off) HIP_OK(hipMemsetAsync(io.d_off, 0, 8, s));
+        return BSDB_OK;
+    }
+    int rc;
+    if ((rc = c->t_size.grow(2 * 4 * io.count))) return rc;
+    TextPlacing pl;
+    pl.rsize = c->t_size.as<uint32_t>();
+    pl.ksize = pl.rsize + io.count;
+    pl.lgrid = text_lane_grid(io.count, c->num_cus);
+    pl.runs.partitions = (uint32_t)io.partitions;
+    for (int p = 0; p <= io.partitions; ++p) pl.runs.bound[p] = text_run_bound(io.count, (uint32_t)io.partitions, (uint32_t)p);
+    pl.pack = {io.d_text, io.bytes, io.d.kpos, io.d.klen, io.d.vpos, io.d.vlen, io.count, nullptr, nullptr, 0};
+    if ((rc = io.B ? text_place_blocked(c, io, pl, s) : text_place_compact(c, io, pl, s))) return rc;
+    if (io.d_blob && pl.blob_bytes) text_pack_launch<false>(c, pl.pack, io.d_off, io.d_blob, pl.blob_bytes, s);
+    uint64_t *const d_addr = pl.roff ? io.d_addr : nullptr;  // (the blocked addresses are k_blk_place's)
+    if (d_addr || io.d_value8)
+        k_text_outputs<<<pl.lgrid, 256, 0, s>>>(pl.runs, io.d_text, io.bytes, io.d.vpos, io.d.vlen, pl.roff, io.count, d_addr,
+                                                 io.d_value8, io.d_value_len);
+    if ((rc = launch_status())) return rc;
+    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = pl.run[p];
+    if (io.h_blob_bytes) *io.h_blob_bytes = pl.blob_bytes;
+    return BSDB_OK;
+}
+
+// bsdb_dev_text_pack(_blocked) after their argument checks
+int text_pack_locked(bsdb_ctx *c, const TextPackIO &io, void *stream) {
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    hipStream_t s = pick(c, stream);
+    Ordered ord(c, s);
+    return text_pack_impl(c, io, s);
 }
 
 // A batch in device memory into a streaming builder of variable-length keys:
@@ -366,6 +393,65 @@ bool write_all(int fd, const uint8_t *buf, uint64_t bytes, uint64_t off) {
     return true;
 }
 
+// What one bsdb_text_build call keeps from chunk to chunk.
+struct TextBuild {
+    bsdb_ctx *c;
+    int sep, partitions;
+    uint32_t B;  // TextPackIO's
+    bool approximate;
+    TextBufs bufs;
+    std::vector<uint8_t> himg;  // the last chunk's image, its runs back to back
+    uint64_t records = 0;       // kept so far
+};
+
+// The device step of one chunk, under the context's lock: the `cut` bytes at
+// h_text go up and are split, the report comes back (k = the records this
+// chunk adds), the buffers grow to the chunk, the records are packed behind
+// files of part_size bytes, and the image comes back into tb.himg.
+int text_chunk_step(TextBuild &tb, const uint8_t *h_text, uint64_t cut, const uint64_t *part_size, uint64_t *report,
+                    uint64_t *run_bytes, uint64_t &k) {
+    bsdb_ctx *c = tb.c;
+    TextBufs &bufs = tb.bufs;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    Ordered ord(c, s);
+    const uint64_t cap = text_max_records(cut);
+    int rc;
+    if ((rc = bufs.text.grow(cut + 16)) || (rc = bufs.desc.grow(4 * 4 * cap))) return rc;
+    if ((rc = h2d_bounce(s, bufs.text.p, h_text, cut))) return rc;
+    uint32_t *desc = bufs.desc.as<uint32_t>();
+    unsigned long long *d_report = bufs.report.as<unsigned long long>();
+    if ((rc = text_split_impl(c, bufs.text.as<const uint8_t>(), cut, (uint32_t)tb.sep, cap, desc, desc + cap, desc + 2 * cap,
+                              desc + 3 * cap, d_report, s)))
+        return rc;
+    HIP_OK(hipMemcpyAsync(report, d_report, 8 * TW_WORDS, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    k = report[TW_RECORDS] - tb.records;
+    tb.records = report[TW_RECORDS];
+    if (k > cap) return BSDB_EIO;
+    if (!k) return BSDB_OK;
+    const uint64_t image_max = tb.B ? text_image_max_blocked(cut, tb.partitions, tb.B) : text_image_max(cut);
+    if ((rc = bufs.image.grow(image_max)) || (rc = bufs.blob.grow(text_blob_max(cut))) || (rc = bufs.off.grow(8 * (k + 1))) ||
+        (rc = bufs.addr.grow(8 * k)) || (tb.approximate && ((rc = bufs.v8.grow(8 * k)) || (rc = bufs.vl.grow(k)))))
+        return rc;
+    const TextPackIO io{bufs.text.as<const uint8_t>(), cut, {desc, desc + cap, desc + 2 * cap, desc + 3 * cap}, k, tb.partitions, tb.B,
+                        part_size, bufs.image.as<uint8_t>(), image_max, run_bytes, bufs.addr.as<uint64_t>(),
+                        bufs.blob.as<uint8_t>(), text_blob_max(cut), bufs.off.as<uint64_t>(), nullptr,
+                        tb.approximate ? bufs.v8.as<uint64_t>() : nullptr, tb.approximate ? bufs.vl.as<uint8_t>() : nullptr};
+    uint64_t image_bytes = 0;
+    if ((rc = text_pack_impl(c, io, s))) return rc;
+    for (int p = 0; p < tb.partitions; ++p) image_bytes += run_bytes[p];
+    try {
+        if (tb.himg.size() < image_bytes) tb.himg.resize(image_bytes);
+    } catch (const std::bad_alloc &) {
+        return BSDB_ENOMEM;
+    }
+    HIP_OK(hipMemcpyAsync(tb.himg.data(), bufs.image.p, image_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,19 +477,10 @@ int bsdb_dev_text_pack(bsdb_ctx *c, const uint8_t *d_text, uint64_t bytes, const
                        const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap, uint64_t *h_run_bytes,
                        uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off, uint64_t *h_blob_bytes,
                        uint64_t *d_value8, uint8_t *d_value_len, void *stream) {
-    if (!c || bytes > TEXT_MAX_BYTES || (bytes && !d_text) || !aligned16(d_text) || count > text_max_records(bytes) ||
-        partitions < 1 || partitions > TEXT_MAX_PARTS || !h_part_size || !h_run_bytes ||
-        (count && (!d_kpos || !d_klen || !d_vpos || !d_vlen)) ||
-        (((uintptr_t)d_kpos | (uintptr_t)d_klen | (uintptr_t)d_vpos | (uintptr_t)d_vlen) & 3) || (!d_blob != !d_off) ||
-        (!d_value8 != !d_value_len) || (((uintptr_t)d_addr | (uintptr_t)d_off | (uintptr_t)d_value8) & 7))
-        return BSDB_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = pick(c, stream);
-    Ordered ord(c, s);
-    const TextDesc d{d_kpos, d_klen, d_vpos, d_vlen};
-    return text_pack_impl(c, d_text, bytes, d, count, partitions, h_part_size, d_image, image_cap, h_run_bytes, d_addr,
-                          d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len, s);
+    const TextPackIO io{d_text, bytes, {d_kpos, d_klen, d_vpos, d_vlen}, count, partitions, 0, h_part_size, d_image, image_cap,
+                        h_run_bytes, d_addr, d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len};
+    if (text_pack_bad_args(c, io)) return BSDB_EINVAL;
+    return text_pack_locked(c, io, stream);
 }
 
 uint64_t bsdb_text_image_max(uint64_t bytes, int partitions, int format, uint32_t block_size) {
@@ -415,21 +492,12 @@ int bsdb_dev_text_pack_blocked(bsdb_ctx *c, const uint8_t *d_text, uint64_t byte
                                uint32_t block_size, const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap,
                                uint64_t *h_run_bytes, uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off,
                                uint64_t *h_blob_bytes, uint64_t *d_value8, uint8_t *d_value_len, void *stream) {
-    if (!c || bytes > TEXT_MAX_BYTES || (bytes && !d_text) || !aligned16(d_text) || count > text_max_records(bytes) ||
-        partitions < 1 || partitions > TEXT_MAX_PARTS || text_bad_block_size(block_size) || !h_part_size || !h_run_bytes ||
-        (count && (!d_kpos || !d_klen || !d_vpos || !d_vlen)) ||
-        (((uintptr_t)d_kpos | (uintptr_t)d_klen | (uintptr_t)d_vpos | (uintptr_t)d_vlen) & 3) || (!d_blob != !d_off) ||
-        (!d_value8 != !d_value_len) || (((uintptr_t)d_addr | (uintptr_t)d_off | (uintptr_t)d_value8) & 7))
-        return BSDB_EINVAL;
+    const TextPackIO io{d_text, bytes, {d_kpos, d_klen, d_vpos, d_vlen}, count, partitions, block_size, h_part_size, d_image, image_cap,
+                        h_run_bytes, d_addr, d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len};
+    if (text_pack_bad_args(c, io) || text_bad_block_size(block_size)) return BSDB_EINVAL;
     for (int p = 0; p < partitions; ++p)
         if ((h_part_size[p] & (TEXT_PAGE - 1)) || h_part_size[p] > TEXT_MAX_FILE_BLOCKED) return BSDB_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = pick(c, stream);
-    Ordered ord(c, s);
-    const TextDesc d{d_kpos, d_klen, d_vpos, d_vlen};
-    return text_pack_blocked_impl(c, d_text, bytes, d, count, partitions, block_size, h_part_size, d_image, image_cap,
-                                  h_run_bytes, d_addr, d_blob, blob_cap, d_off, h_blob_bytes, d_value8, d_value_len, s);
+    return text_pack_locked(c, io, stream);
 }
 
 int bsdb_builder_add_dev_var(bsdb_builder *b, const uint8_t *d_blob, const uint64_t *d_off, uint64_t count,
@@ -482,7 +550,7 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
     }
     // the chunk size and the report on the device
     uint64_t chunk = 0;
-    TextBufs bufs;
+    TextBuild tb{c, sep, partitions, blocked ? block_size : 0, approximate != 0};
     {
         std::lock_guard<std::mutex> g(c->mu);
         HIP_OK(hipSetDevice(c->device));
@@ -490,12 +558,12 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
         chunk = blocked ? text_chunk_bytes_blocked(c->text_chunk, free_b, partitions, block_size)
                         : text_chunk_bytes(c->text_chunk, free_b);
-        int rc = bufs.report.grow(8 * TW_WORDS);
+        int rc = tb.bufs.report.grow(8 * TW_WORDS);
         if (rc) return rc;
-        HIP_OK(hipMemsetAsync(bufs.report.p, 0, 8 * TW_WORDS, c->stream));
+        HIP_OK(hipMemsetAsync(tb.bufs.report.p, 0, 8 * TW_WORDS, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
-    std::vector<uint8_t> hbuf, himg;
+    std::vector<uint8_t> hbuf;
     try {
         hbuf.resize(chunk);
     } catch (const std::bad_alloc &) {
@@ -508,7 +576,7 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
         bsdb_builder *b;
         ~BuilderGuard() { (void)bsdb_builder_free(b); }
     } guard{b};
-    uint64_t records = 0;
+    const TextBufs &bufs = tb.bufs;
     for (int f = 0; f < nfiles; ++f) {
         TextReader &r = in[f];
         uint64_t fill = 0;  // bytes in hbuf: the tail carried over the last cut, then what was read
@@ -525,59 +593,13 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
             if (!fill) break;  // (the end of the file, nothing carried)
             const uint64_t cut = text_cut(hbuf.data(), fill, r.eof);
             if (!cut) return BSDB_E2BIG;  // a full buffer without a line end: a line longer than the chunk
-            uint64_t run_bytes[TEXT_MAX_PARTS] = {}, blob_bytes = 0, k = 0, image_bytes = 0;
-            {
-                std::lock_guard<std::mutex> g(c->mu);
-                HIP_OK(hipSetDevice(c->device));
-                hipStream_t s = c->stream;
-                Ordered ord(c, s);
-                const uint64_t cap = text_max_records(cut);
-                if ((rc = bufs.text.grow(cut + 16)) || (rc = bufs.desc.grow(4 * 4 * cap))) return rc;
-                if ((rc = h2d_bounce(s, bufs.text.p, hbuf.data(), cut))) return rc;
-                uint32_t *desc = bufs.desc.as<uint32_t>();
-                const TextDesc d{desc, desc + cap, desc + 2 * cap, desc + 3 * cap};
-                unsigned long long *d_report = bufs.report.as<unsigned long long>();
-                if ((rc = text_split_impl(c, bufs.text.as<const uint8_t>(), cut, (uint32_t)sep, cap, desc, desc + cap,
-                                          desc + 2 * cap, desc + 3 * cap, d_report, s)))
-                    return rc;
-                HIP_OK(hipMemcpyAsync(report, d_report, 8 * TW_WORDS, hipMemcpyDeviceToHost, s));
-                HIP_OK(hipStreamSynchronize(s));
-                k = report[TW_RECORDS] - records;
-                records = report[TW_RECORDS];
-                if (k > cap) return BSDB_EIO;
-                if (k) {
-                    const uint64_t image_max = blocked ? text_image_max_blocked(cut, partitions, block_size) : text_image_max(cut);
-                    if ((rc = bufs.image.grow(image_max)) || (rc = bufs.blob.grow(text_blob_max(cut))) ||
-                        (rc = bufs.off.grow(8 * (k + 1))) || (rc = bufs.addr.grow(8 * k)) ||
-                        (approximate && ((rc = bufs.v8.grow(8 * k)) || (rc = bufs.vl.grow(k)))))
-                        return rc;
-                    uint64_t *const v8 = approximate ? bufs.v8.as<uint64_t>() : nullptr;
-                    uint8_t *const vl = approximate ? bufs.vl.as<uint8_t>() : nullptr;
-                    rc = blocked ? text_pack_blocked_impl(c, bufs.text.as<const uint8_t>(), cut, d, k, partitions, block_size,
-                                                          part_size, bufs.image.as<uint8_t>(), image_max, run_bytes,
-                                                          bufs.addr.as<uint64_t>(), bufs.blob.as<uint8_t>(), text_blob_max(cut),
-                                                          bufs.off.as<uint64_t>(), &blob_bytes, v8, vl, s)
-                                 : text_pack_impl(c, bufs.text.as<const uint8_t>(), cut, d, k, partitions, part_size,
-                                                  bufs.image.as<uint8_t>(), image_max, run_bytes, bufs.addr.as<uint64_t>(),
-                                                  bufs.blob.as<uint8_t>(), text_blob_max(cut), bufs.off.as<uint64_t>(),
-                                                  &blob_bytes, v8, vl, s);
-                    if (rc) return rc;
-                    for (int p = 0; p < partitions; ++p) image_bytes += run_bytes[p];
-                    try {
-                        if (himg.size() < image_bytes) himg.resize(image_bytes);
-                    } catch (const std::bad_alloc &) {
-                        return BSDB_ENOMEM;
-                    }
-                    HIP_OK(hipMemcpyAsync(himg.data(), bufs.image.p, image_bytes, hipMemcpyDeviceToHost, s));
-                    HIP_OK(hipStreamSynchronize(s));
-                    if ((rc = launch_status())) return rc;
-                }
-            }
+            uint64_t run_bytes[TEXT_MAX_PARTS] = {}, k = 0;
+            if ((rc = text_chunk_step(tb, hbuf.data(), cut, part_size, report, run_bytes, k))) return rc;
             if (k) {
                 // the image's runs lie back to back: P plain copies, each appended to its file
                 uint64_t at = 0;
                 for (int p = 0; p < partitions; ++p) {
-                    if (!write_all(part[p].fd, himg.data() + at, run_bytes[p], part_size[p])) return BSDB_EFILE;
+                    if (!write_all(part[p].fd, tb.himg.data() + at, run_bytes[p], part_size[p])) return BSDB_EFILE;
                     at += run_bytes[p];
                     part_size[p] += run_bytes[p];
                 }

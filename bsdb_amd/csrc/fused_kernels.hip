@@ -33,8 +33,11 @@
 // k_overflow_fallback recount the keys with direct atomics.  Every spin is
 // bounded (FU_SPIN_MAX polls) and a timeout aborts every workgroup
 // (error word, results not added).
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "hash_kernels.hip"  // the 13-byte tile readers and geometry (u32x4a, D13_Q, ...)
 
 namespace bsdb {
 

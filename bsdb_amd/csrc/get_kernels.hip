@@ -7,7 +7,8 @@
 //                 -> address (get_decode, get_plan.hpp) -> record header ->
 //                 key compare; writes where each value lies and how long it is
 //   k_get_gather  copies the values into the packed output, driven by the
-//                 output: a thread owns an aligned 16-byte piece of it
+//                 output: a thread owns an aligned 16-byte piece of it (the
+//                 piece loop, its search and its store: piece_copy.hpp)
 // The key readers, the hash and the lookup are verify's (verify_kernels.hip).
 //
 // index.db is untrusted: every address is bounds-tested against the image
@@ -20,6 +21,7 @@
 #include <stdint.h>
 
 #include "get_plan.hpp"
+#include "piece_copy.hpp"
 #include "verify_kernels.hip"
 
 namespace bsdb {
@@ -132,18 +134,6 @@ __global__ __launch_bounds__(256) void k_get_locate(MphView v, GetDb db, GetArgs
     get_locate<KIND>(v, db, a);
 }
 
-// The query whose value holds output byte o: the last q in [lo, hi] with
-// voff[q] <= o (voff[lo] <= o is the caller's).  Empty values share their
-// offset with the next query, so the last one is the one with bytes.
-__device__ __forceinline__ uint64_t get_owner(const uint64_t *voff, uint64_t lo, uint64_t hi, uint64_t o) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (voff[mid] <= o) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 struct GatherArgs {
     const uint8_t *image;
     uint64_t image_bytes;
@@ -155,73 +145,20 @@ struct GatherArgs {
     uint64_t value_bytes;
 };
 
-// Piece k is the 16 bytes at (values & ~15) + 16 k: output bytes
-// [16 k - mis, 16 k - mis + 16) cut to [0, value_bytes).  A thread finds the
-// queries its piece overlaps by a search in voff -- the wave's first and last
-// lanes search all of it, the others between those two results -- assembles
-// the piece from its sources in registers and stores it once (the first and
-// last pieces of the whole output byte by byte, inside the output).  The work
-// of a piece does not depend on how long the values around it are: a run of
-// empty values is stepped over by the search, a long value is shared by as
-// many threads as it has pieces.
+
+// The piece loop of piece_copy.hpp over the packed values: a piece's owners
+// are the queries whose values overlap it, found in voff; a run of empty
+// values is stepped over by the search, a long value is shared by as many
+// threads as it has pieces.
 __global__ __launch_bounds__(256) void k_get_gather(GatherArgs a) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t mis = (uint32_t)((uintptr_t)a.values & 15);
-    uint8_t *const aligned = a.values - mis;
-    const uint64_t pieces = get_gather_pieces(a.value_bytes, mis);
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t wbase = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); wbase < pieces; wbase += stride) {
-        const uint64_t k = wbase + lane;
-        const bool active = k < pieces;
-        // this piece's output bytes [o0, o1); the wave's [w0, w1)
-        const uint64_t klast = wbase + 63 < pieces ? wbase + 63 : pieces - 1;
-        auto first_of = [&](uint64_t kk) -> uint64_t { return kk ? kk * 16 - mis : 0; };
-        auto end_of = [&](uint64_t kk) -> uint64_t {
-            const uint64_t e = kk * 16 + 16 - mis;
-            return e < a.value_bytes ? e : a.value_bytes;
-        };
-        const uint64_t w0 = first_of(wbase), w1 = end_of(klast);
-        uint64_t qlo = 0, qhi = 0;
-        if (lane == 0) qlo = get_owner(a.voff, 0, a.nq - 1, w0);
-        if (lane == 63) qhi = get_owner(a.voff, 0, a.nq - 1, w1 - 1);
-        qlo = __shfl(qlo, 0, 64);
-        qhi = __shfl(qhi, 63, 64);
-        if (!active) continue;  // (no wave-wide operation below)
-        const uint64_t o0 = first_of(k), o1 = end_of(k);
-        const uint32_t j0 = (uint32_t)(o0 + mis - k * 16);  // the piece's first valid byte
-        uint64_t lo = 0, hi = 0;
-        uint64_t q = qlo;
-        bool searched = false;
-        for (uint64_t o = o0; o < o1;) {
-            if (!searched || a.voff[q + 1] <= o) {  // past q's value: the owner of o, within the wave's range
-                q = get_owner(a.voff, q < qhi && searched ? q + 1 : q, qhi, o);
-                searched = true;
-            }
-            const uint64_t vs = a.voff[q], ve = a.voff[q + 1];
-            if (vs > o || ve <= o) break;  // offsets that are no scan of lengths: the rest stays zero
-            const uint64_t run_end = ve < o1 ? ve : o1;
-            const uint64_t sp = a.src[q] * a.scale + (o - vs);
-            for (uint64_t t = o; t < run_end; t += 8) {
-                const uint32_t nb = run_end - t < 8 ? (uint32_t)(run_end - t) : 8;
-                const uint64_t p = sp + (t - o);
-                const uint64_t x = (p < a.image_bytes ? sel_gload64(a.image, a.image_bytes, p) : 0) & low_bytes_mask(nb);
-                const uint32_t j = j0 + (uint32_t)(t - o0);  // byte of the piece, 0..15
-                if (j < 8) {
-                    lo |= x << (8 * j);
-                    if (j) hi |= x >> (64 - 8 * j);
-                } else {
-                    hi |= x << (8 * (j - 8));
-                }
-            }
-            o = run_end;
-        }
-        uint8_t *dst = aligned + k * 16;
-        if (o1 - o0 == 16) {
-            *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(lo, hi);
-        } else {
-            for (uint32_t j = j0; j < j0 + (uint32_t)(o1 - o0); ++j) dst[j] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))));
-        }
-    }
+    uint64_t qlo, qhi;
+    piece_loop(
+        a.values, a.value_bytes, [&](uint64_t w0, uint64_t w1) { piece_wave_owners(a.voff, a.nq, w0, w1, qlo, qhi); },
+        [&](Piece &pc) {
+            piece_runs(pc, a.voff, qlo, qhi, [&](uint64_t q, uint64_t vs, uint64_t o, uint64_t e) {
+                pc.copy(a.image, a.image_bytes, a.src[q] * a.scale + (o - vs), pc.j0 + (uint32_t)(o - pc.o0), (uint32_t)(e - o));
+            });
+        });
 }
 
 }  // namespace bsdb

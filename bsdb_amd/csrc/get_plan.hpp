@@ -2,9 +2,9 @@
 // allocates and launches, decided on the host from plain numbers: the layout
 // of the resident kv.db image (get_layout), whether an open fits the free
 // memory (get_open_fits), how the host forms cut their queries into chunks
-// (get_host_chunk), the grids of the locate and gather launches, and the
-// address decode with its bounds test (get_decode), which the locate kernel
-// calls too.  C++17 without HIP or getenv, so the arithmetic runs (and is
+// (get_host_chunk), the grid of the locate launch (the gather's is
+// piece_grid, piece_plan.hpp), and the address decode with its bounds test
+// (get_decode), which the locate kernel calls too.  C++17 without HIP or getenv, so the arithmetic runs (and is
 // checked, tests/get_plan_check.cpp) without a GPU.
 //   read/SyncReader.java:44-57, read/kv/PartitionedKVReader.java:78-82,
 //   read/kv/BlockedKVReader.java:42-52, read/kv/BaseKVReader.java:16-31
@@ -13,11 +13,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define BSDB_HD __host__ __device__
-#else
-#define BSDB_HD
-#endif
+#include "piece_plan.hpp"  // the gather's grid (piece_grid); BSDB_HD
 
 namespace bsdb {
 
@@ -80,20 +76,6 @@ inline uint64_t get_host_chunk(uint64_t batch, uint32_t key_len) {
 inline uint32_t get_locate_grid(uint64_t nq, int num_cus) {
     const uint64_t cus = (uint64_t)std::max(1, num_cus);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(nq >> 8) + ((nq & 255) != 0), cus * 16, GET_GRID_MAX}));
-}
-
-// k_get_gather: a thread per aligned 16-byte piece of the output, grid-stride.
-// `misalign` = the output pointer's low 4 bits: the pieces start at the
-// aligned address below it.
-BSDB_HD inline uint64_t get_gather_pieces(uint64_t value_bytes, uint32_t misalign) {
-    // ceil((value_bytes + misalign) / 16) without a sum that could wrap
-    return value_bytes ? (value_bytes >> 4) + (((value_bytes & 15) + (misalign & 15) + 15) >> 4) : 0;
-}
-
-inline uint32_t get_gather_grid(uint64_t value_bytes, uint32_t misalign, int num_cus) {
-    const uint64_t cus = (uint64_t)std::max(1, num_cus);
-    const uint64_t pieces = get_gather_pieces(value_bytes, misalign);
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(pieces >> 8) + ((pieces & 255) != 0), cus * 32, GET_GRID_MAX}));
 }
 
 // Where an address says its record is.  ok: the 3-byte header [pos, pos + 3)

@@ -2714,19 +2714,6 @@ struct SelArgs {
     uint64_t *pay;           // MODE 1: input positions
 };
 
-__device__ __forceinline__ uint64_t sel_gload64(const uint8_t *base, uint64_t limit, uint64_t pos) {
-    const uint64_t a = pos & ~3ULL;
-    const uint32_t sh = (uint32_t)(pos & 3) * 8;
-    auto ld = [&](uint64_t x) -> uint32_t {
-        if (x + 4 <= limit) return *reinterpret_cast<const uint32_t *>(base + x);
-        uint32_t w = 0;
-        for (int b = 0; b < 4; ++b)
-            if (x + b < limit) w |= (uint32_t)base[x + b] << (8 * b);
-        return w;
-    };
-    return funnel64(ld(a), ld(a + 4), ld(a + 8), sh);
-}
-
 template <int MODE, int KIND>
 __global__ __launch_bounds__(256) void k_sel(SelArgs a) {
     typedef unsigned int u32x4w __attribute__((ext_vector_type(4), aligned(4)));

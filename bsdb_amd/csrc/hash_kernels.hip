@@ -18,6 +18,7 @@
 // (variable-length keys, and fixed lengths up to 32 B on computed offsets),
 // k_pass1_d13 (13-byte keys past 288 bins), k_pass1 (generic: tails, the
 // signature and direct-atomic epilogues, comparison front ends).  DESIGN.md §4.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -909,11 +910,6 @@ constexpr uint32_t VARE_PRE_VECS = 192;            // 16-B vectors per group pre
 constexpr uint32_t VARE_STAGE_VECS = 288;          // 16-B vectors per wave stage (4.5 KiB)
 constexpr int VARE_STAGE_WORDS = VARE_STAGE_VECS * 4 + 20;  // + slack for the 17-dword key reads
 constexpr int VARE_PERM_WORDS = 128;               // per wave: a group's keys sorted short-first
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), l) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, l);
-}
 
 // k_pass1_vare's general-length paths (keys over 64 B, groups over the stage),
 // out of line: the unrolled hot loop then carries one copy of each.

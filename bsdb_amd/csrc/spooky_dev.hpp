@@ -134,6 +134,27 @@ __device__ __forceinline__ uint64_t funnel64(uint32_t d0, uint32_t d1, uint32_t 
     return ((uint64_t)hi << 32) | lo;
 }
 
+// The bounded reader: the 8 bytes at byte `pos` of (base, limit) by aligned
+// dword loads; bytes at or past `limit` read as 0 and are never touched.
+__device__ __forceinline__ uint64_t sel_gload64(const uint8_t *base, uint64_t limit, uint64_t pos) {
+    const uint64_t a = pos & ~3ULL;
+    const uint32_t sh = (uint32_t)(pos & 3) * 8;
+    auto ld = [&](uint64_t x) -> uint32_t {
+        if (x + 4 <= limit) return *reinterpret_cast<const uint32_t *>(base + x);
+        uint32_t w = 0;
+        for (int b = 0; b < 4; ++b)
+            if (x + b < limit) w |= (uint32_t)base[x + b] << (8 * b);
+        return w;
+    };
+    return funnel64(ld(a), ld(a + 4), ld(a + 8), sh);
+}
+
+// lane l's 64-bit value, the same in every lane
+__device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), l) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, l);
+}
+
 // ---- 32-bit-half formulation --------------------------------------------
 // The same arithmetic with every 64-bit word held as two VGPRs: xor = 2
 // v_xor_b32, rotate = 2 v_alignbit_b32, add = v_add_co_u32 + v_addc_co_u32.

@@ -3,8 +3,9 @@
 // text_plan.hpp).  A record's place depends on a greedy recurrence (a record
 // that does not fit the rest of its block opens a new one); it is placed
 // without a lane walking a run:
-//   k_blk_sizes   a record per lane: its size, its key bytes, and its size as
-//                 a SMALL record (0 for a large one); S = the scan of the last
+//   k_text_sizes  (text_kernels.hip, with ssize) a record per lane: its size,
+//                 its key bytes, and its size as a SMALL record (0 for a
+//                 large one); S = the scan of the last
 //   k_blk_tile    a workgroup per TEXT_TILE records, S's slice in LDS:
 //                 next[a] = the first record that does not fit a block opened
 //                 at a, capped at the run's end (a binary search, in LDS
@@ -25,9 +26,9 @@
 //   k_blk_place   a record per lane: its address and its position in the image
 //                 as a small record (PS) and as a large one (PL); both lists
 //                 are sorted, a record of the other kind is an empty interval
-//   k_text_pack_blocked   driven by the output as k_text_pack: a thread owns
-//                 an aligned 16-byte piece, finds its records in PS and PL,
-//                 and stores it once; bytes of no record are zeros
+//   k_text_pack_blocked   driven by the output, by the piece loop of
+//                 piece_copy.hpp and k_text_pack's record writer: a piece's
+//                 records are found in PS and PL; bytes of no record are zeros
 // The chain of block starts runs through the whole chunk: next is capped at
 // the run's end, so every run's first record is a block start (a large first
 // record stands for the first small one after it: it adds nothing to S).
@@ -39,28 +40,6 @@
 #include "text_kernels.hip"
 
 namespace bsdb {
-
-// the run of record i: the last p with bound[p] <= i (empty runs share their bound)
-__device__ __forceinline__ uint32_t text_run_of(const TextRuns &runs, uint64_t i) {
-    uint32_t lo = 0, hi = runs.partitions - 1;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (runs.bound[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void k_blk_sizes(const uint32_t *klen, const uint32_t *vlen, uint64_t count, uint32_t B,
-                                                   uint32_t *rsize, uint32_t *ksize, uint32_t *ssize) {
-    const uint64_t step = (uint64_t)gridDim.x * 256;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < count; r += step) {
-        const uint32_t kl = text_klen(klen[r]), sz = 3 + kl + text_vlen(vlen[r]);
-        rsize[r] = sz;
-        ksize[r] = kl;
-        ssize[r] = sz > B ? 0 : sz;
-    }
-}
 
 // Workgroup t: records [t TEXT_TILE, ...).  S[count + 1]; next[count]; exl[count] = (last, exit).
 __global__ __launch_bounds__(256) void k_blk_tile(TextRuns runs, const uint64_t *S, uint64_t count, uint32_t B, uint32_t *next,
@@ -270,116 +249,59 @@ struct TextPackBlocked {
     uint32_t B;
 };
 
-// The piece framework of k_text_pack.  The owner of output byte o is the last
-// small record with PS <= o if o lies within its bytes, else the last large
-// record with PL <= o if o lies within its bytes, else nobody: the byte is 0
-// up to the next entry of either list.
+// The piece loop of piece_copy.hpp and the record writer of k_text_pack.  The
+// owner of output byte o is the last small record with PS <= o if o lies
+// within its bytes, else the last large record with PL <= o if o lies within
+// its bytes, else nobody: the byte is 0 up to the next entry of either list.
 __global__ __launch_bounds__(256) void k_text_pack_blocked(TextPackBlocked b) {
     const TextPack &a = b.t;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t mis = (uint32_t)((uintptr_t)a.dst & 15);
-    uint8_t *const aligned = a.dst - mis;
-    const uint64_t pieces = text_pack_pieces(a.out_bytes, mis);
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t wbase = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); wbase < pieces; wbase += stride) {
-        const uint64_t k = wbase + lane;
-        const bool active = k < pieces;
-        const uint64_t klast = wbase + 63 < pieces ? wbase + 63 : pieces - 1;
-        auto first_of = [&](uint64_t kk) -> uint64_t { return kk ? kk * 16 - mis : 0; };
-        auto end_of = [&](uint64_t kk) -> uint64_t {
-            const uint64_t e = kk * 16 + 16 - mis;
-            return e < a.out_bytes ? e : a.out_bytes;
-        };
-        const uint64_t w0 = first_of(wbase), w1 = end_of(klast);
-        uint64_t slo = 0, shi = 0, llo = 0, lhi = 0;
-        if (lane == 0) {
-            slo = get_owner(b.PS, 0, a.count - 1, w0);
-            llo = get_owner(b.PL, 0, a.count - 1, w0);
-        }
-        if (lane == 63) {
-            shi = get_owner(b.PS, 0, a.count - 1, w1 - 1);
-            lhi = get_owner(b.PL, 0, a.count - 1, w1 - 1);
-        }
-        slo = __shfl(slo, 0, 64);
-        llo = __shfl(llo, 0, 64);
-        shi = __shfl(shi, 63, 64);
-        lhi = __shfl(lhi, 63, 64);
-        if (!active) continue;  // (no wave-wide operation below)
-        const uint64_t o0 = first_of(k), o1 = end_of(k);
-        const uint32_t j0 = (uint32_t)(o0 + mis - k * 16);  // the piece's first valid byte
-        uint64_t lo = 0, hi = 0;
-        auto put = [&](uint64_t x, uint32_t j, uint32_t nb) {
-            x &= low_bytes_mask(nb);
-            if (j < 8) {
-                lo |= x << (8 * j);
-                if (j) hi |= x >> (64 - 8 * j);
-            } else {
-                hi |= x << (8 * (j - 8));
-            }
-        };
-        // bytes [o, e) of the image from record q, which starts at rs
-        auto emit = [&](uint64_t q, uint64_t rs, uint64_t o, uint64_t e, uint32_t kl, uint32_t vl) {
-            const uint32_t x0 = (uint32_t)(o - rs), x1 = (uint32_t)(e - rs);
-            const uint32_t jr = j0 + (uint32_t)(o - o0);
-            if (x0 < 3) {
-                const uint64_t h = (uint64_t)kl | (uint64_t)(vl >> 8) << 8 | (uint64_t)(vl & 0xFF) << 16;
-                const uint32_t he = x1 < 3 ? x1 : 3;
-                put(h >> (8 * x0), jr, he - x0);
-            }
-            for (int seg = 0; seg < 2; ++seg) {
-                const uint32_t s0 = seg ? 3 + kl : 3, s1 = seg ? 3 + kl + vl : 3 + kl;
-                const uint64_t src = seg ? a.vpos[q] : a.kpos[q];
-                const uint32_t xb = x0 > s0 ? x0 : s0, xe = x1 < s1 ? x1 : s1;
-                for (uint32_t x = xb; x < xe; x += 8) {
-                    const uint32_t nb = xe - x < 8 ? xe - x : 8;
-                    const uint64_t p = src + (x - s0);
-                    put(p < a.bytes ? sel_gload64(a.text, a.bytes, p) : 0, jr + (x - x0), nb);
+    uint64_t slo, shi, llo, lhi;
+    piece_loop(
+        a.dst, a.out_bytes,
+        [&](uint64_t w0, uint64_t w1) {
+            piece_wave_owners(b.PS, a.count, w0, w1, slo, shi);
+            piece_wave_owners(b.PL, a.count, w0, w1, llo, lhi);
+        },
+        [&](Piece &pc) {
+            uint64_t hint = a.count;  // the record after the small one just written
+            for (uint64_t o = pc.o0; o < pc.o1;) {
+                // a small record?
+                uint64_t q = hint, rs = 0;
+                uint32_t kl = 0, vl = 0, sz = 0;
+                auto load = [&](const uint64_t *list) {
+                    rs = list[q];
+                    kl = text_klen(a.klen[q]), vl = text_vlen(a.vlen[q]), sz = 3 + kl + vl;
+                };
+                // record q, which starts at rs, owns o: its bytes up to the piece's end
+                auto emit = [&]() {
+                    const uint64_t e = rs + sz < pc.o1 ? rs + sz : pc.o1;
+                    text_put_record<true>(pc, a, q, kl, vl, (uint32_t)(o - rs), (uint32_t)(e - rs), pc.j0 + (uint32_t)(o - pc.o0));
+                    o = e;
+                };
+                if (q < a.count) load(b.PS);
+                if (q >= a.count || rs != o || sz > b.B) {  // (a small record that starts at o is the last entry at or before o)
+                    q = get_owner(b.PS, slo, shi, o);
+                    load(b.PS);
                 }
+                hint = a.count;
+                if (sz <= b.B && rs <= o && o < rs + sz) {
+                    hint = q + 1;
+                    emit();
+                    continue;
+                }
+                uint64_t nearest = rs > o ? rs : b.PS[q + 1];  // the next list entry past o (PS[count] ends the image)
+                // a large one?
+                q = get_owner(b.PL, llo, lhi, o);
+                load(b.PL);
+                if (sz > b.B && rs <= o && o < rs + sz) {
+                    emit();
+                    continue;
+                }
+                const uint64_t nl = rs > o ? rs : b.PL[q + 1];
+                nearest = nl < nearest ? nl : nearest;
+                o = nearest > o && nearest < pc.o1 ? nearest : pc.o1;  // zeros up to there
             }
-        };
-        uint64_t hint = a.count;  // the record after the small one just written
-        for (uint64_t o = o0; o < o1;) {
-            // a small record?
-            uint64_t q = hint, rs = 0;
-            uint32_t kl = 0, vl = 0, sz = 0;
-            auto load = [&](const uint64_t *list) {
-                rs = list[q];
-                kl = text_klen(a.klen[q]), vl = text_vlen(a.vlen[q]), sz = 3 + kl + vl;
-            };
-            if (q < a.count) load(b.PS);
-            if (q >= a.count || rs != o || sz > b.B) {  // (a small record that starts at o is the last entry at or before o)
-                q = get_owner(b.PS, slo, shi, o);
-                load(b.PS);
-            }
-            hint = a.count;
-            if (sz <= b.B && rs <= o && o < rs + sz) {
-                const uint64_t e = rs + sz < o1 ? rs + sz : o1;
-                emit(q, rs, o, e, kl, vl);
-                hint = q + 1;
-                o = e;
-                continue;
-            }
-            uint64_t nearest = rs > o ? rs : b.PS[q + 1];  // the next list entry past o (PS[count] ends the image)
-            // a large one?
-            q = get_owner(b.PL, llo, lhi, o);
-            load(b.PL);
-            if (sz > b.B && rs <= o && o < rs + sz) {
-                const uint64_t e = rs + sz < o1 ? rs + sz : o1;
-                emit(q, rs, o, e, kl, vl);
-                o = e;
-                continue;
-            }
-            const uint64_t nl = rs > o ? rs : b.PL[q + 1];
-            nearest = nl < nearest ? nl : nearest;
-            o = nearest > o && nearest < o1 ? nearest : o1;  // zeros up to there
-        }
-        uint8_t *dst = aligned + k * 16;
-        if (o1 - o0 == 16) {
-            *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(lo, hi);
-        } else {
-            for (uint32_t j = j0; j < j0 + (uint32_t)(o1 - o0); ++j) dst[j] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))));
-        }
-    }
+        });
 }
 
 }  // namespace bsdb

@@ -14,10 +14,11 @@
 //                     pass 0 counts and flags, pass 1 (after the scan of the
 //                     flags) writes the kept lines' descriptors in input order
 //   k_text_sizes      a record per lane: its bytes in the image and in the blob
-//   k_text_pack       driven by the output, as k_get_gather: a thread owns an
-//                     aligned 16-byte piece of the destination, finds the
-//                     records it overlaps in the size scan, assembles the
-//                     piece in registers and stores it once
+//                     (and, for the blocked layout, as a small record)
+//   k_text_pack       driven by the output, by the piece loop k_get_gather
+//                     runs (piece_copy.hpp): the owners of a 16-byte piece of
+//                     the destination are found in the size scan; what the
+//                     kernel adds is the record writer, text_put_record
 //   k_text_outputs    a record per lane: its address and its value head
 // No lane walks a line: a 32 KB value or a 1 MB junk line costs what a
 // 20-byte line costs.  Every read of the text in the pack goes through the
@@ -26,7 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "get_kernels.hip"
+#include "piece_copy.hpp"
 #include "text_plan.hpp"
 
 namespace bsdb {
@@ -220,14 +221,17 @@ __global__ __launch_bounds__(256) void k_text_records(TextSplit a) {
 __device__ __forceinline__ uint32_t text_klen(uint32_t klen) { return klen < TEXT_MAX_KEY ? klen : TEXT_MAX_KEY; }
 __device__ __forceinline__ uint32_t text_vlen(uint32_t vlen) { return vlen < TEXT_MAX_VALUE ? vlen : TEXT_MAX_VALUE; }
 
-// record r's bytes in the image (header + key + value) and in the key blob
-__global__ __launch_bounds__(256) void k_text_sizes(const uint32_t *klen, const uint32_t *vlen, uint64_t count, uint32_t *rsize,
-                                                    uint32_t *ksize) {
+// record r's bytes in the image (header + key + value) and in the key blob;
+// ssize (the blocked layout, else null): its bytes as a SMALL record of blocks
+// of B bytes, 0 for a large one
+__global__ __launch_bounds__(256) void k_text_sizes(const uint32_t *klen, const uint32_t *vlen, uint64_t count, uint32_t B,
+                                                    uint32_t *rsize, uint32_t *ksize, uint32_t *ssize) {
     const uint64_t step = (uint64_t)gridDim.x * 256;
     for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < count; r += step) {
-        const uint32_t kl = text_klen(klen[r]);
-        rsize[r] = 3 + kl + text_vlen(vlen[r]);
+        const uint32_t kl = text_klen(klen[r]), sz = 3 + kl + text_vlen(vlen[r]);
+        rsize[r] = sz;
         ksize[r] = kl;
+        if (ssize) ssize[r] = sz > B ? 0 : sz;
     }
 }
 
@@ -241,90 +245,41 @@ struct TextPack {
     uint64_t out_bytes;
 };
 
-// IMAGE: a record is [kLen u8][vLen u16 BE][key][value]
+// Bytes [x0, x1) of record q, whose lengths are kl and vl, to the piece from
+// byte jr.  IMAGE: the record is [kLen u8][vLen u16 BE][key][value]
 // (SimpleCompactKVWriter.java:36-42); otherwise its key alone (the blob the
-// hash kernels read).  Piece k is the 16 bytes at (dst & ~15) + 16 k: output
-// bytes [16 k - mis, 16 k - mis + 16) cut to [0, out_bytes).  The search for
-// the records of a piece is k_get_gather's (get_owner): the wave's first and
-// last lanes search the whole scan, the others between those two results.
-// One 16-byte store per piece; the first and last pieces of the destination
-// byte by byte, inside the destination.
+// hash kernels read).
+template <bool IMAGE>
+__device__ __forceinline__ void text_put_record(Piece &pc, const TextPack &a, uint64_t q, uint32_t kl, uint32_t vl, uint32_t x0,
+                                                uint32_t x1, uint32_t jr) {
+    const uint32_t hdr = IMAGE ? 3 : 0;
+    if (IMAGE && x0 < 3) {
+        const uint64_t h = (uint64_t)kl | (uint64_t)(vl >> 8) << 8 | (uint64_t)(vl & 0xFF) << 16;
+        const uint32_t e = x1 < 3 ? x1 : 3;
+        pc.put(h >> (8 * x0), jr, e - x0);
+    }
+    // the key's and the value's part of [x0, x1)
+    for (int seg = 0; seg < (IMAGE ? 2 : 1); ++seg) {
+        const uint32_t s0 = seg ? hdr + kl : hdr, s1 = seg ? hdr + kl + vl : hdr + kl;
+        const uint64_t src = seg ? a.vpos[q] : a.kpos[q];
+        const uint32_t b = x0 > s0 ? x0 : s0, e = x1 < s1 ? x1 : s1;
+        if (b < e) pc.copy(a.text, a.bytes, src + (b - s0), jr + (b - x0), e - b);
+    }
+}
+
+// The piece loop of piece_copy.hpp over the destination: a piece's owners are
+// the records whose bytes overlap it, found in the scan of their sizes.
 template <bool IMAGE>
 __global__ __launch_bounds__(256) void k_text_pack(TextPack a) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t mis = (uint32_t)((uintptr_t)a.dst & 15);
-    uint8_t *const aligned = a.dst - mis;
-    const uint64_t pieces = text_pack_pieces(a.out_bytes, mis);
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t wbase = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); wbase < pieces; wbase += stride) {
-        const uint64_t k = wbase + lane;
-        const bool active = k < pieces;
-        const uint64_t klast = wbase + 63 < pieces ? wbase + 63 : pieces - 1;
-        auto first_of = [&](uint64_t kk) -> uint64_t { return kk ? kk * 16 - mis : 0; };
-        auto end_of = [&](uint64_t kk) -> uint64_t {
-            const uint64_t e = kk * 16 + 16 - mis;
-            return e < a.out_bytes ? e : a.out_bytes;
-        };
-        const uint64_t w0 = first_of(wbase), w1 = end_of(klast);
-        uint64_t qlo = 0, qhi = 0;
-        if (lane == 0) qlo = get_owner(a.off, 0, a.count - 1, w0);
-        if (lane == 63) qhi = get_owner(a.off, 0, a.count - 1, w1 - 1);
-        qlo = __shfl(qlo, 0, 64);
-        qhi = __shfl(qhi, 63, 64);
-        if (!active) continue;  // (no wave-wide operation below)
-        const uint64_t o0 = first_of(k), o1 = end_of(k);
-        const uint32_t j0 = (uint32_t)(o0 + mis - k * 16);  // the piece's first valid byte
-        uint64_t lo = 0, hi = 0;
-        // nb <= 8 bytes (the low ones of x) to piece bytes j .. j + nb - 1
-        auto put = [&](uint64_t x, uint32_t j, uint32_t nb) {
-            x &= low_bytes_mask(nb);
-            if (j < 8) {
-                lo |= x << (8 * j);
-                if (j) hi |= x >> (64 - 8 * j);
-            } else {
-                hi |= x << (8 * (j - 8));
-            }
-        };
-        uint64_t q = qlo;
-        bool searched = false;
-        for (uint64_t o = o0; o < o1;) {
-            if (!searched || a.off[q + 1] <= o) {  // past q's record: the owner of o, within the wave's range
-                q = get_owner(a.off, q < qhi && searched ? q + 1 : q, qhi, o);
-                searched = true;
-            }
-            const uint64_t rs = a.off[q], re = a.off[q + 1];
-            if (rs > o || re <= o) break;  // offsets that are no scan of sizes: the rest stays zero
-            const uint64_t run_end = re < o1 ? re : o1;
-            const uint32_t kl = text_klen(a.klen[q]), vl = text_vlen(a.vlen[q]);
-            const uint32_t hdr = IMAGE ? 3 : 0;
-            // record bytes [x0, x1) go to piece bytes from jr
-            const uint32_t x0 = (uint32_t)(o - rs), x1 = (uint32_t)(run_end - rs);
-            const uint32_t jr = j0 + (uint32_t)(o - o0);
-            if (IMAGE && x0 < 3) {
-                const uint64_t h = (uint64_t)kl | (uint64_t)(vl >> 8) << 8 | (uint64_t)(vl & 0xFF) << 16;
-                const uint32_t e = x1 < 3 ? x1 : 3;
-                put(h >> (8 * x0), jr, e - x0);
-            }
-            // the key's and the value's part of [x0, x1), 8 source bytes a step
-            for (int seg = 0; seg < (IMAGE ? 2 : 1); ++seg) {
-                const uint32_t s0 = seg ? hdr + kl : hdr, s1 = seg ? hdr + kl + vl : hdr + kl;
-                const uint64_t src = seg ? a.vpos[q] : a.kpos[q];
-                const uint32_t b = x0 > s0 ? x0 : s0, e = x1 < s1 ? x1 : s1;
-                for (uint32_t x = b; x < e; x += 8) {
-                    const uint32_t nb = e - x < 8 ? e - x : 8;
-                    const uint64_t p = src + (x - s0);
-                    put(p < a.bytes ? sel_gload64(a.text, a.bytes, p) : 0, jr + (x - x0), nb);
-                }
-            }
-            o = run_end;
-        }
-        uint8_t *dst = aligned + k * 16;
-        if (o1 - o0 == 16) {
-            *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(lo, hi);
-        } else {
-            for (uint32_t j = j0; j < j0 + (uint32_t)(o1 - o0); ++j) dst[j] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))));
-        }
-    }
+    uint64_t qlo, qhi;
+    piece_loop(
+        a.dst, a.out_bytes, [&](uint64_t w0, uint64_t w1) { piece_wave_owners(a.off, a.count, w0, w1, qlo, qhi); },
+        [&](Piece &pc) {
+            piece_runs(pc, a.off, qlo, qhi, [&](uint64_t q, uint64_t rs, uint64_t o, uint64_t e) {
+                text_put_record<IMAGE>(pc, a, q, text_klen(a.klen[q]), text_vlen(a.vlen[q]), (uint32_t)(o - rs), (uint32_t)(e - rs),
+                                       pc.j0 + (uint32_t)(o - pc.o0));
+            });
+        });
 }
 
 // The runs of the partition rule (text_run_bound) and where each lands:
@@ -336,6 +291,17 @@ struct TextRuns {
     uint64_t file_base[TEXT_MAX_PARTS];
 };
 
+// the run of record i: the last p with bound[p] <= i (empty runs share their bound)
+__device__ __forceinline__ uint32_t text_run_of(const TextRuns &runs, uint64_t i) {
+    uint32_t lo = 0, hi = runs.partitions - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (runs.bound[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 // A record per lane: addr = p << 56 | offset (SimpleCompactKVWriter.java:62-73,
 // PartitionedKVWriter.java:82-96) and, for index.approximate, the value head:
 // the first min(vlen, 8) value bytes, the rest 0, and that length
@@ -346,13 +312,8 @@ __global__ __launch_bounds__(256) void k_text_outputs(TextRuns runs, const uint8
     const uint64_t step = (uint64_t)gridDim.x * 256;
     for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < count; r += step) {
         if (addr) {
-            uint32_t lo = 0, hi = runs.partitions - 1;  // the last p with bound[p] <= r (empty runs share their bound)
-            while (lo < hi) {
-                const uint32_t mid = lo + (hi - lo + 1) / 2;
-                if (runs.bound[mid] <= r) lo = mid;
-                else hi = mid - 1;
-            }
-            addr[r] = (uint64_t)lo << 56 | (runs.file_base[lo] + roff[r]);
+            const uint32_t p = text_run_of(runs, r);
+            addr[r] = (uint64_t)p << 56 | (runs.file_base[p] + roff[r]);
         }
         if (value8) {
             const uint32_t vl = text_vlen(vlen[r]), l = vl < 8 ? vl : 8;

@@ -1,6 +1,6 @@
 // text_plan.hpp -- what the text front end (capi_text.hip, text_kernels.hip)
-// allocates and launches, decided on the host from plain numbers: the grids,
-// the most records a chunk can hold (text_max_records), a chunk's device
+// allocates and launches, decided on the host from plain numbers: the grids
+// (the packs' is piece_grid, piece_plan.hpp), the most records a chunk can hold (text_max_records), a chunk's device
 // footprint once its lines and separators are counted (text_footprint), the
 // chunk size (text_chunk_bytes), the runs of the partition rule
 // (text_run_bound), where a buffer of a file is cut (text_cut), and the
@@ -16,11 +16,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define BSDB_HD __host__ __device__
-#else
-#define BSDB_HD
-#endif
+#include "piece_plan.hpp"  // the packs' grid (piece_grid); BSDB_HD
 
 namespace bsdb {
 
@@ -62,17 +58,6 @@ inline uint32_t text_count_grid(uint64_t bytes) {
 inline uint32_t text_lane_grid(uint64_t items, int num_cus) {
     const uint64_t cus = (uint64_t)std::max(1, num_cus);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(items >> 8) + ((items & 255) != 0), cus * 16, TEXT_GRID_MAX}));
-}
-
-// k_text_pack: a thread per aligned 16-byte piece of the destination,
-// grid-stride.  `misalign` = the destination pointer's low 4 bits.
-BSDB_HD inline uint64_t text_pack_pieces(uint64_t out_bytes, uint32_t misalign) {
-    return out_bytes ? (out_bytes >> 4) + (((out_bytes & 15) + (misalign & 15) + 15) >> 4) : 0;
-}
-inline uint32_t text_pack_grid(uint64_t out_bytes, uint32_t misalign, int num_cus) {
-    const uint64_t cus = (uint64_t)std::max(1, num_cus);
-    const uint64_t pieces = text_pack_pieces(out_bytes, misalign);
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(pieces >> 8) + ((pieces & 255) != 0), cus * 32, TEXT_GRID_MAX}));
 }
 
 // Device bytes of one chunk of `bytes` text bytes with `lines` lines and

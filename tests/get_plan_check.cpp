@@ -58,8 +58,8 @@ int main() {
         printf("],");
         J("open_bytes", get_open_bytes(l.total, n, approx != 0)), J("fits", get_open_fits(l.total, n, approx != 0, free_b));
         J("chunk", get_host_chunk(batch, (uint32_t)key_len));
-        J("locate_grid", get_locate_grid(nq, (int)num_cus)), J("pieces", get_gather_pieces(value_bytes, (uint32_t)mis));
-        J("gather_grid", get_gather_grid(value_bytes, (uint32_t)mis, (int)num_cus));
+        J("locate_grid", get_locate_grid(nq, (int)num_cus)), J("pieces", piece_count(value_bytes, (uint32_t)mis));
+        J("gather_grid", piece_grid(value_bytes, (uint32_t)mis, (int)num_cus));
         J("ok", r.ok), J("part", r.part), J("pos", r.pos), J("limit", r.limit, "}\n");
     }
     return 0;

@@ -237,6 +237,47 @@ def test_gather_edges_through_the_device_forms(tmp_path):
             check(db.get_var(kblob, koff), np.zeros(n, np.uint8), vals)  # the host form: the same bytes
 
 
+@pytest.fixture(scope="module")
+def short_located(tmp_path_factory):
+    """Three queries with values of 1, 20 and 9 bytes, located once in a 50-record database: ctx, db and, for the
+    first query alone and for all three, (src, voff, the value bytes)."""
+    _need_gpu()
+    from bsdb_amd import Context, kvfiles
+    d = tmp_path_factory.mktemp("get_short")
+    keys = [b"k%d" % i for i in range(50)]
+    vals = [bytes(range(i, i + n)) for i, n in enumerate([1, 20, 9] + [5] * 47)]
+    kv, ip = str(d / "kv.db"), str(d / "index.db")
+    kblob, koff = pack(keys)
+    with Context(0) as ctx:
+        addr = kvfiles.write_compact(kv, 1, kblob, koff, *kvfiles.pack_values(vals))
+        with ctx.mph_build_index_var(kblob, koff, 4, addr, ip) as mph, mph.open_db(kv, 1, ip) as db:
+            cases = []
+            for nq in (1, 3):
+                qblob, qoff = pack(keys[:nq])
+                src, vlen, status, _ = ctx.db_locate_var(db, torch.from_numpy(qblob.copy()).cuda(),
+                                                         torch.from_numpy(qoff.astype(np.int64)).cuda())
+                assert not status.any().item()
+                cases.append((src, ctx.edge_offsets(vlen), b"".join(vals[:nq])))
+            yield ctx, db, cases
+
+
+@pytest.mark.parametrize("mis", range(16))
+def test_gather_short_outputs_at_every_misalignment(short_located, mis):
+    """A 1-byte and a 30-byte output at `mis` bytes past an aligned address, between guards: an output shorter than
+    a piece, whose first piece is its last, and one of two or three pieces with both ends partial."""
+    ctx, db, cases = short_located
+    for src, voff, want in cases:
+        assert len(want) in (1, 30)
+        big = torch.full((mis + len(want) + 37,), 0xA5, dtype=torch.uint8, device="cuda")
+        view = big[mis: mis + len(want)]
+        assert view.data_ptr() % 16 == mis
+        ctx.db_gather(db, src, voff, values=view, value_bytes=len(want))
+        torch.cuda.synchronize()
+        got = big.cpu().numpy()
+        assert got[mis: mis + len(want)].tobytes() == want
+        assert (got[:mis] == 0xA5).all() and (got[mis + len(want):] == 0xA5).all()
+
+
 @pytest.mark.parametrize("block", [4096, 8192])
 def test_blocked_layout(tmp_path, block):
     _need_gpu()

@@ -120,15 +120,16 @@ def prepare(ctx, sizes):
     return len(text), recs, t, desc, k
 
 
-def check_pack(ctx, tmp, sizes, parts, B, before=None, prepared=None):
+def check_pack(ctx, tmp, sizes, parts, B, before=None, prepared=None, lead=3):
     """Packs the records of `sizes` into blocks of B bytes, into an image view exactly as large as the oracle's
-    image at a misaligned address between guard bytes and a guarded address array, and compares everything."""
+    image at a misaligned address (`lead` past an aligned one) between guard bytes and a guarded address array, and
+    compares everything."""
     nbytes, recs, t, desc, k = prepared or prepare(ctx, sizes)
     before = before or [0] * parts
     image, runs, addr = oracle_chunk(str(tmp), recs, parts, B, before)
-    ibuf, iview = guarded_u8(len(image), 3)
+    ibuf, iview = guarded_u8(len(image), lead)
     abuf, aview, al = guarded_i64(max(k, 1))
-    assert iview.data_ptr() % 16 == 3 and aview.data_ptr() % 16 == 8
+    assert iview.data_ptr() % 16 == lead and aview.data_ptr() % 16 == 8
     out = ctx.text_pack(t, desc, k, parts, before, nbytes=nbytes, image=iview, addr=aview, block_size=B)
     torch.cuda.synchronize()
     assert out["run_bytes"] == runs and all(r % PAGE == 0 for r in runs)
@@ -141,7 +142,7 @@ def check_pack(ctx, tmp, sizes, parts, B, before=None, prepared=None):
     bad = np.flatnonzero(ga != addr)
     assert bad.size == 0, (bad[:5], [hex(int(x)) for x in ga[bad[:5]]], [hex(int(x)) for x in addr[bad[:5]]])
     h = ibuf.cpu().numpy()
-    assert (h[:3] == GUARD).all() and (h[3 + len(image):] == GUARD).all()
+    assert (h[:lead] == GUARD).all() and (h[lead + len(image):] == GUARD).all()
     h = abuf.cpu().numpy()
     assert (h[:al] == IGUARD).all() and (h[al + max(k, 1):] == IGUARD).all()
     return out
@@ -181,6 +182,14 @@ def test_rule_table(ctx, tmp_path, name):
 def test_fewer_records_than_partitions(ctx, tmp_path):
     out = check_pack(ctx, tmp_path, [100, 5000, 7], 8, PAGE)
     assert out["run_bytes"].count(0) == 5
+
+
+@pytest.mark.parametrize("mis", range(16))
+def test_three_short_records_at_every_misalignment(ctx, tmp_path, mis):
+    """The smallest blocked image, one block that three short records open, at every misalignment of the
+    destination: its first and last pieces are partial at every one but 0."""
+    out = check_pack(ctx, tmp_path, [5, 9, 12], 1, PAGE, lead=mis)
+    assert out["run_bytes"] == [PAGE]
 
 
 # ---- 2. tile and wave edges ----------------------------------------------------------------------------------

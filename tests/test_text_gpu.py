@@ -283,6 +283,29 @@ def test_pack(ctx, parts, count):
     check_guard_i64(abuf, al, k), check_guard_i64(obuf, ol, k + 1), check_guard_i64(vbuf, vlead, k)
 
 
+@pytest.mark.parametrize("mis", range(16))
+def test_pack_short_destinations_at_every_misalignment(ctx, mis):
+    """Three short records, and the first of them alone: a 17- and a 5-byte image, a 4- and a 1-byte key blob, each
+    at `mis` bytes past an aligned address between guards.  Destinations shorter than a piece: their first piece is
+    their last where mis + bytes <= 16, and they straddle two partial pieces where it is more."""
+    text = b"a b\ncd e\nf gh\n"
+    t, desc, recs, _ = check_split(ctx, text, b" ")
+    assert len(recs) == 3
+    for k in (1, 3):
+        image, _ = R.image_of(recs[:k])
+        blob = b"".join(key for _, key, _, _ in recs[:k])
+        assert (len(image), len(blob)) == ((5, 1) if k == 1 else (17, 4))
+        ibuf, iview = guarded_u8(len(image), mis)
+        bbuf, bview = guarded_u8(len(blob), mis)
+        assert iview.data_ptr() % 16 == mis and bview.data_ptr() % 16 == mis
+        out = ctx.text_pack(t, desc, k, 1, [0], nbytes=len(text), image=iview, blob=bview)
+        torch.cuda.synchronize()
+        assert out["run_bytes"] == [len(image)]
+        assert out["image"].cpu().numpy().tobytes() == image
+        assert out["blob"].cpu().numpy().tobytes() == blob
+        check_guard_u8(ibuf, mis, len(image)), check_guard_u8(bbuf, mis, len(blob))
+
+
 def test_pack_refuses_a_small_destination(ctx):
     from bsdb_amd.native import BsdbError
     text = b"a b\nc d\n"

@@ -61,8 +61,8 @@ int main() {
         const TextFootprint f = text_footprint(bytes, lines, seps, approx != 0);
         printf("{");
         J("max_records", text_max_records(bytes)), J("blocks", text_blocks(bytes)), J("count_grid", text_count_grid(bytes));
-        J("lane_grid", text_lane_grid(items, (int)num_cus)), J("pieces", text_pack_pieces(out_bytes, (uint32_t)mis));
-        J("pack_grid", text_pack_grid(out_bytes, (uint32_t)mis, (int)num_cus));
+        J("lane_grid", text_lane_grid(items, (int)num_cus)), J("pieces", piece_count(out_bytes, (uint32_t)mis));
+        J("pack_grid", piece_grid(out_bytes, (uint32_t)mis, (int)num_cus));
         J("image_max", text_image_max(bytes)), J("blob_max", text_blob_max(bytes));
         J("fp_split", f.split), J("fp_pack", f.pack), J("fp_total", f.total);
         J("chunk", text_chunk_bytes(requested, free_b)), J("bad_sep", text_bad_separator((int)(int64_t)sep));
