@@ -20,8 +20,16 @@ one literal byte (never a regular expression), a line must fit one chunk.
 
 Command line, mirroring ``Builder``'s flags::
 
-    python -m bsdb_amd.builder -i INPUT [-i INPUT ...] -o OUT_DIR [-s SEP] [-cb BITS] [-a] [-v] [-p PARTITIONS]
+    python -m bsdb_amd.builder -i INPUT [-i INPUT ...] -o OUT_DIR [-s SEP] [-cb BITS] [-a] [-v] [-vv] [-p PARTITIONS]
                                [-l {compact,blocked}] [-bs BLOCK_SIZE]
+    python -m bsdb_amd.builder --check -i INPUT [-i INPUT ...] -o DB_DIR [-s SEP]
+
+``-vv`` (``build_text(verify_values=True)``) is the reference's ``-v``
+(tools/Builder.java:184-228): the input is read a second time and every
+record's value is compared with what the database returns for its key, on the
+device (``bsdb_db_check_text``, bsdb_amd/csrc/check_kernels.hip).  ``--check``
+builds nothing and runs that comparison of an existing database directory
+against text files (``check_text``).  Both exit with status 2 on a mismatch.
 """
 from __future__ import annotations
 
@@ -30,7 +38,7 @@ import os
 import sys
 from typing import Optional
 
-from .native import BSDB_EDUP, BsdbError, Context, DuplicateKeyError
+from .native import BSDB_EDUP, CHECK_STATUS_NAMES, BsdbError, Context, DuplicateKeyError
 from .writer import VerifyError
 
 COMPRESSED_SUFFIXES = (".gz", ".zstd", ".zst")
@@ -102,13 +110,18 @@ def _duplicate_error(ctx: Context, kv_base: str, partitions: int, fmt: int = 0, 
 
 def build_text(inputs, out_dir: str, separator=" ", checksum_bits: int = 4, approximate: bool = False,
                partitions: int = 8, verify: bool = False, device: int = 0, chunk_bytes: Optional[int] = None,
-               layout: str = "compact", block_size: int = 4096) -> dict:
+               layout: str = "compact", block_size: int = 4096, verify_values: bool = False) -> dict:
     """Builds the database of the records in ``inputs`` into ``out_dir`` and
     returns the text report (native.TEXT_FIELDS).  ``layout``: "compact" (the
     reference's -c) or "blocked" (the reference's default) in blocks of
     ``block_size`` bytes.  ``verify=True`` checks the
     finished files on the device (Mph.verify_kv) and raises VerifyError when
-    they are not clean.  A duplicate key raises DuplicateKeyError (``.keys``:
+    they are not clean.  ``verify_values=True`` then opens the database on the
+    MPHF just built and checks it against the same files, key -> value
+    (Database.check_text; an approximate build's index_a.db too), and raises
+    VerifyError carrying that dict when a record is not OK or the OK records
+    are not all the text's; a clean check's dict is returned as
+    ``report["values"]``.  A duplicate key raises DuplicateKeyError (``.keys``:
     up to 16 of them)."""
     if layout not in LAYOUTS:
         raise ValueError("layout is 'compact' or 'blocked'")
@@ -134,9 +147,47 @@ def build_text(inputs, out_dir: str, separator=" ", checksum_bits: int = 4, appr
                 rep = mph.verify_kv(kv, partitions, index, index_a, approximate, fmt=fmt, block_size=block_size)
                 if not rep["ok"]:
                     raise VerifyError(rep)
+            if verify_values:
+                for approx in ([False, True] if approximate else [False]):
+                    with mph.open_db(kv, partitions, index_a if approx else index, approx, fmt, block_size) as db:
+                        res = db.check_text(files, separator)
+                    res["db_records"] = report["records"]
+                    res["complete"] = res["check"]["ok"] == report["records"]
+                    if not res["ok"] or not res["complete"]:
+                        raise VerifyError(res)
+                    report.setdefault("values", res)  # (the exact check's dict rides with the report)
         finally:
             mph.close()
     return report
+
+
+def check_text(inputs, db_dir: str, separator=" ", device: int = 0, approximate: Optional[bool] = None,
+               bad_cap: int = 16, strict: bool = False) -> dict:
+    """Checks the database directory ``db_dir`` (opened as BSDBReader opens
+    it: config.properties, hash.dump, the kv.db files) against the records of
+    ``inputs``, key -> value, on the device.  Returns the dict of
+    Database.check_text plus ``db_records`` (the database's record count) and
+    ``complete``: the OK records are as many as the database holds, so the
+    text is not only in the database but all of it (for inputs without a
+    repeated key).  ``strict=True`` raises VerifyError carrying the dict when a
+    record is not OK."""
+    from .reader import BSDBReader
+    files = input_files(inputs)
+    with BSDBReader(db_dir, approximate=approximate, device=device) as r:
+        res = r.db.check_text(files, separator, bad_cap)
+        res["db_records"] = r.db.info()["n"]
+    res["complete"] = res["check"]["ok"] == res["db_records"]
+    if strict and not res["ok"]:
+        raise VerifyError(res)
+    return res
+
+
+def format_check(res: dict) -> str:
+    """The counts on one line, then ``path:offset status`` for the records held in ``bad``."""
+    lines = [" ".join(f"{k}={v}" for k, v in res["check"].items() if k != "first_bad") +
+             f" db_records={res['db_records']} complete={str(res['complete']).lower()}"]
+    lines += [f"{path}:{off} {CHECK_STATUS_NAMES[st] if st < len(CHECK_STATUS_NAMES) else st}" for path, off, st in res["bad"]]
+    return "\n".join(lines)
 
 
 def parser() -> argparse.ArgumentParser:
@@ -153,6 +204,11 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("-cb", "--checksum-bits", type=int, default=4, help="checksum bit length, default 4")
     ap.add_argument("-a", "--approximate", action="store_true", help="approximate mode: index_a.db holds the first 8 value bytes")
     ap.add_argument("-v", "--verify", action="store_true", help="verify the generated index on the device")
+    ap.add_argument("-vv", "--verify-values", action="store_true",
+                    help="after the build, read the input again and compare every record's value with what the "
+                         "database returns for its key, on the device; exit status 2 on a mismatch")
+    ap.add_argument("--check", action="store_true",
+                    help="build nothing: check the database in -o against the input, key -> value; exit status 2 on a mismatch")
     ap.add_argument("-p", "--partitions", type=int, default=8, help="kv.db partition files, 1..128, default 8")
     ap.add_argument("-l", "--layout", choices=sorted(LAYOUTS), default="compact",
                     help="kv.db layout, default compact; the reference's own default is blocked")
@@ -167,10 +223,24 @@ def main(argv=None) -> int:
     files = []
     for i in a.input:
         files += input_files(i)
-    report = build_text(files, a.output, a.separator, a.checksum_bits, a.approximate, a.partitions, a.verify,
-                        layout=a.layout, block_size=a.block_size)
+    if a.check:
+        res = check_text(files, a.output, a.separator)
+        if not a.quiet:
+            print(format_check(res))
+        return 0 if res["ok"] else 2
+    try:
+        report = build_text(files, a.output, a.separator, a.checksum_bits, a.approximate, a.partitions, a.verify,
+                            layout=a.layout, block_size=a.block_size, verify_values=a.verify_values)
+    except VerifyError as e:
+        if "check" not in e.report:  # (-v's report: as before)
+            raise
+        if not a.quiet:
+            print(format_check(e.report))
+        return 2
     if not a.quiet:
-        print(" ".join(f"{k}={v}" for k, v in report.items()))
+        print(" ".join(f"{k}={v}" for k, v in report.items() if k != "values"))
+        if "values" in report:
+            print(format_check(report["values"]))
     return 0
 
 

@@ -10,7 +10,8 @@
 // (which keys are duplicates, with its plan dup_plan.hpp), capi_get.hip
 // (batched get of a resident database, with its plan get_plan.hpp),
 // capi_text.hip (text lines into records, kv.db files in the compact or the
-// blocked layout and a database, with its plan text_plan.hpp).
+// blocked layout and a database, with its plan text_plan.hpp), capi_check.hip
+// (a database checked against text input, with its plan check_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -53,6 +54,7 @@
 #include "get_kernels.hip"
 #include "text_kernels.hip"
 #include "text_blocked_kernels.hip"
+#include "check_kernels.hip"
 
 using namespace bsdb;
 
@@ -180,6 +182,7 @@ struct bsdb_ctx {
     DevBuf t_size{bufs, true}, t_roff{bufs, true};
     DevBuf t_blk{bufs, true};  // the blocked layout's placement workspace (text_place_workspace)
     uint64_t text_chunk = 0;  // bsdb_text_set_chunk (0 = default)
+    DevBuf k_cmp{bufs, true}, k_coff{bufs, true};  // the check (capi_check.hip): the bytes to compare per record, their scan
     // live profiling: event pairs per launch, per kind
     bool profiling = false;
     struct Rec { hipEvent_t a, b; int kind; uint64_t keys; };
@@ -1050,3 +1053,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_dup.hip"
 #include "capi_get.hip"
 #include "capi_text.hip"
+#include "capi_check.hip"

@@ -374,6 +374,51 @@ struct TextReader {
     }
 };
 
+// The files of a call, opened in the order given; total_bytes: the sum of their sizes.
+int text_open_inputs(const char *const *paths, int nfiles, std::vector<TextReader> &in, uint64_t &total_bytes) {
+    total_bytes = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        struct stat st;
+        if ((in[f].fd = ::open(paths[f], O_RDONLY)) < 0 || fstat(in[f].fd, &st) != 0) return BSDB_EFILE;
+        total_bytes += (uint64_t)std::max<off_t>(st.st_size, 0);
+    }
+    return BSDB_OK;
+}
+
+// The read loop of bsdb_text_build and bsdb_db_check_text: every file a chunk
+// at a time through hbuf (`chunk` bytes), cut after the chunk's last line end
+// (text_cut), the tail carried to the next chunk; chunks never span files.
+// step(file, file offset of the chunk's first byte, the chunk, its bytes) per
+// chunk; BSDB_E2BIG for a line longer than a chunk.
+template <class Step>
+int text_read_chunks(std::vector<TextReader> &in, std::vector<uint8_t> &hbuf, uint64_t chunk, Step &&step) {
+    for (size_t f = 0; f < in.size(); ++f) {
+        TextReader &r = in[f];
+        uint64_t fill = 0;  // bytes in hbuf: the tail carried over the last cut, then what was read
+        for (;;) {
+            const int64_t got = r.fill(hbuf.data() + fill, chunk - fill);
+            if (got < 0) return BSDB_EFILE;
+            fill += (uint64_t)got;
+            if (fill == chunk && !r.eof) {  // (a file that ends with the buffer: its last line needs no terminator)
+                uint8_t probe;
+                const ssize_t pr = pread(r.fd, &probe, 1, (off_t)r.pos);
+                if (pr < 0) return BSDB_EFILE;
+                r.eof = pr == 0;
+            }
+            if (!fill) break;  // (the end of the file, nothing carried)
+            const uint64_t cut = text_cut(hbuf.data(), fill, r.eof);
+            if (!cut) return BSDB_E2BIG;  // a full buffer without a line end: a line longer than the chunk
+            const int rc = step((int)f, r.pos - fill, hbuf.data(), cut);
+            if (rc) return rc;
+            // the tail after the cut opens the next chunk
+            fill -= cut;
+            if (fill) memmove(hbuf.data(), hbuf.data() + cut, fill);
+            if (r.eof && !fill) break;
+        }
+    }
+    return BSDB_OK;
+}
+
 // the device buffers of one bsdb_text_build call (freed when it ends)
 struct TextBufs {
     DevBuf text, desc, image, blob, off, addr, v8, vl, report;
@@ -537,11 +582,8 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
     // the inputs and the partition files
     std::vector<TextReader> in((size_t)nfiles);
     uint64_t total_bytes = 0;
-    for (int f = 0; f < nfiles; ++f) {
-        struct stat st;
-        if ((in[f].fd = ::open(paths[f], O_RDONLY)) < 0 || fstat(in[f].fd, &st) != 0) return BSDB_EFILE;
-        total_bytes += (uint64_t)std::max<off_t>(st.st_size, 0);
-    }
+    int rc = text_open_inputs(paths, nfiles, in, total_bytes);
+    if (rc) return rc;
     Fd part[TEXT_MAX_PARTS];
     uint64_t part_size[TEXT_MAX_PARTS] = {};
     for (int p = 0; p < partitions; ++p) {
@@ -558,8 +600,7 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
         chunk = blocked ? text_chunk_bytes_blocked(c->text_chunk, free_b, partitions, block_size)
                         : text_chunk_bytes(c->text_chunk, free_b);
-        int rc = tb.bufs.report.grow(8 * TW_WORDS);
-        if (rc) return rc;
+        if ((rc = tb.bufs.report.grow(8 * TW_WORDS))) return rc;
         HIP_OK(hipMemsetAsync(tb.bufs.report.p, 0, 8 * TW_WORDS, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
@@ -570,50 +611,28 @@ int bsdb_text_build_layout(bsdb_ctx *c, const char *const *paths, int nfiles, in
         return BSDB_ENOMEM;
     }
     bsdb_builder *b = nullptr;
-    int rc = bsdb_builder_open(c, 0, total_bytes / 16 + 1024, total_bytes / 2 + 65536, approximate, 0, 0, &b);
-    if (rc) return rc;
+    if ((rc = bsdb_builder_open(c, 0, total_bytes / 16 + 1024, total_bytes / 2 + 65536, approximate, 0, 0, &b))) return rc;
     struct BuilderGuard {
         bsdb_builder *b;
         ~BuilderGuard() { (void)bsdb_builder_free(b); }
     } guard{b};
     const TextBufs &bufs = tb.bufs;
-    for (int f = 0; f < nfiles; ++f) {
-        TextReader &r = in[f];
-        uint64_t fill = 0;  // bytes in hbuf: the tail carried over the last cut, then what was read
-        for (;;) {
-            const int64_t got = r.fill(hbuf.data() + fill, chunk - fill);
-            if (got < 0) return BSDB_EFILE;
-            fill += (uint64_t)got;
-            if (fill == chunk && !r.eof) {  // (a file that ends with the buffer: its last line needs no terminator)
-                uint8_t probe;
-                const ssize_t pr = pread(r.fd, &probe, 1, (off_t)r.pos);
-                if (pr < 0) return BSDB_EFILE;
-                r.eof = pr == 0;
-            }
-            if (!fill) break;  // (the end of the file, nothing carried)
-            const uint64_t cut = text_cut(hbuf.data(), fill, r.eof);
-            if (!cut) return BSDB_E2BIG;  // a full buffer without a line end: a line longer than the chunk
-            uint64_t run_bytes[TEXT_MAX_PARTS] = {}, k = 0;
-            if ((rc = text_chunk_step(tb, hbuf.data(), cut, part_size, report, run_bytes, k))) return rc;
-            if (k) {
-                // the image's runs lie back to back: P plain copies, each appended to its file
-                uint64_t at = 0;
-                for (int p = 0; p < partitions; ++p) {
-                    if (!write_all(part[p].fd, tb.himg.data() + at, run_bytes[p], part_size[p])) return BSDB_EFILE;
-                    at += run_bytes[p];
-                    part_size[p] += run_bytes[p];
-                }
-                if ((rc = builder_add_dev(b, bufs.blob.as<const uint8_t>(), bufs.off.as<const uint64_t>(), k,
-                                          bufs.addr.as<const uint64_t>(), approximate ? bufs.v8.as<const uint64_t>() : nullptr,
-                                          approximate ? bufs.vl.as<const uint8_t>() : nullptr, c->stream)))
-                    return rc;
-            }
-            // the tail after the cut opens the next chunk
-            fill -= cut;
-            if (fill) memmove(hbuf.data(), hbuf.data() + cut, fill);
-            if (r.eof && !fill) break;
+    rc = text_read_chunks(in, hbuf, chunk, [&](int, uint64_t, const uint8_t *h_text, uint64_t cut) -> int {
+        uint64_t run_bytes[TEXT_MAX_PARTS] = {}, k = 0;
+        int r2 = text_chunk_step(tb, h_text, cut, part_size, report, run_bytes, k);
+        if (r2 || !k) return r2;
+        // the image's runs lie back to back: P plain copies, each appended to its file
+        uint64_t at = 0;
+        for (int p = 0; p < partitions; ++p) {
+            if (!write_all(part[p].fd, tb.himg.data() + at, run_bytes[p], part_size[p])) return BSDB_EFILE;
+            at += run_bytes[p];
+            part_size[p] += run_bytes[p];
         }
-    }
+        return builder_add_dev(b, bufs.blob.as<const uint8_t>(), bufs.off.as<const uint64_t>(), k, bufs.addr.as<const uint64_t>(),
+                               approximate ? bufs.v8.as<const uint64_t>() : nullptr,
+                               approximate ? bufs.vl.as<const uint8_t>() : nullptr, c->stream);
+    });
+    if (rc) return rc;
     for (int p = 0; p < partitions; ++p) {
         const int fd = part[p].fd;
         part[p].fd = -1;

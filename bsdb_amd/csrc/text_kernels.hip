@@ -302,6 +302,16 @@ __device__ __forceinline__ uint32_t text_run_of(const TextRuns &runs, uint64_t i
     return lo;
 }
 
+// The value head index.approximate stores for a value of `vlen` bytes at
+// `vpos` of the text: its first l = min(vlen, 8) bytes, the rest 0
+// (BSDBWriter.java:140-142).  k_text_outputs writes it, the check of a database
+// against its text (check_kernels.hip) compares the slot with it.
+__device__ __forceinline__ uint64_t text_value_head(const uint8_t *text, uint64_t bytes, uint64_t vpos, uint32_t vlen, uint32_t &l) {
+    const uint32_t vl = text_vlen(vlen);
+    l = vl < 8 ? vl : 8;
+    return (vpos < bytes ? sel_gload64(text, bytes, vpos) : 0) & low_bytes_mask(l);
+}
+
 // A record per lane: addr = p << 56 | offset (SimpleCompactKVWriter.java:62-73,
 // PartitionedKVWriter.java:82-96) and, for index.approximate, the value head:
 // the first min(vlen, 8) value bytes, the rest 0, and that length
@@ -316,9 +326,8 @@ __global__ __launch_bounds__(256) void k_text_outputs(TextRuns runs, const uint8
             addr[r] = (uint64_t)p << 56 | (runs.file_base[p] + roff[r]);
         }
         if (value8) {
-            const uint32_t vl = text_vlen(vlen[r]), l = vl < 8 ? vl : 8;
-            const uint64_t p = vpos[r];
-            value8[r] = (p < bytes ? sel_gload64(text, bytes, p) : 0) & low_bytes_mask(l);
+            uint32_t l;
+            value8[r] = text_value_head(text, bytes, vpos[r], vlen[r], l);
             value_len[r] = (uint8_t)l;
         }
     }

@@ -160,6 +160,8 @@ SIGNATURES = [
                                         _vp, C.POINTER(_u64), _vp, _vp, _vp]),
     ("bsdb_text_build_layout", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, C.c_char_p, _i, _i, _u32, _u32, _i, C.c_char_p,
                                     C.c_char_p, _vp, C.POINTER(_vp)]),
+    ("bsdb_dev_db_check", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    ("bsdb_db_check_text", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, _vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
 ]
 
 TEXT_WORDS = 10
@@ -175,6 +177,13 @@ GET_FIELDS = ("queries", "found", "rejected", "key_mismatch", "bad_addr", "value
 GET_FOUND, GET_REJECTED, GET_KEY_MISMATCH, GET_BAD_ADDR = 0, 1, 2, 3  # a query's status byte
 DB_INFO_WORDS = 8
 DB_INFO_FIELDS = ("n", "partitions", "format", "block_size", "approximate", "image_bytes", "index_bytes", "batch")
+
+CHECK_WORDS = 8
+# the check report's words in the header's order (uint64_t[BSDB_CHECK_WORDS])
+CHECK_FIELDS = ("records", "ok", "rejected", "key_mismatch", "bad_addr", "value_len", "value_bytes", "first_bad")
+CHECK_OK, CHECK_VALUE_LEN, CHECK_VALUE_BYTES = 0, 4, 5  # a record's status byte; 1 .. 3 are the get's
+CHECK_NONE = (1 << 64) - 1  # first_bad when every record is OK
+CHECK_STATUS_NAMES = CHECK_FIELDS[1:7]  # a status byte's name is its counter's
 
 BSDB_EVERIFY = -74
 VERIFY_WORDS = 8
@@ -359,7 +368,7 @@ class Context:
         return a.value, b.value
 
     # ---- live per-kernel timing (HIP events on the launch stream)
-    PASS1, PASS2, SCAN = 0, 1, 2
+    PASS1, PASS2, SCAN, CHECK_VALUES = 0, 1, 2, 3
 
     def set_profiling(self, on: bool):
         _check("bsdb_set_profiling", lib().bsdb_set_profiling(self._h, 1 if on else 0))
@@ -954,6 +963,37 @@ class Context:
             db._h, _ptr(src), _ptr(voff), nq, _ptr(values), value_bytes, _stream(stream)))
         return values[:value_bytes]
 
+    @staticmethod
+    def check_report(device):
+        """A fresh device report for db_check: int64[CHECK_WORDS], zero with first_bad = UINT64_MAX (-1)."""
+        import torch
+        report = torch.zeros(CHECK_WORDS, dtype=torch.int64, device=device)
+        report[CHECK_WORDS - 1] = -1
+        return report
+
+    def db_check(self, db: "Database", text, vpos, vlen, src, dbvlen, status, nbytes: Optional[int] = None,
+                 count: Optional[int] = None, record_base: int = 0, report=None, stream=None):
+        """bsdb_dev_db_check: the text's values (descriptors vpos / vlen int32
+        of text_split) against the database's (src int64, dbvlen int32, status
+        uint8 of db_locate_var for the same records' keys).  `status` is
+        rewritten in place to the check's; `report` (Context.check_report,
+        made here when not given) accumulates.  Returns (status, report)."""
+        import torch
+        if nbytes is None:
+            nbytes = text.numel()
+        if count is None:
+            count = status.numel()
+        if report is None:
+            report = self.check_report(text.device)
+        if (vpos.dtype != torch.int32 or vlen.dtype != torch.int32 or src.dtype != torch.int64 or dbvlen.dtype != torch.int32
+                or status.dtype != torch.uint8 or report.dtype != torch.int64 or report.numel() < CHECK_WORDS
+                or min(vpos.numel(), vlen.numel(), src.numel(), dbvlen.numel(), status.numel()) < count):
+            raise ValueError("vpos / vlen / dbvlen int32[count], src int64[count], status uint8[count], report int64[CHECK_WORDS]")
+        _check("bsdb_dev_db_check", lib().bsdb_dev_db_check(
+            db._h, _ptr(text), nbytes, _ptr(vpos), _ptr(vlen), _ptr(src), _ptr(dbvlen), _ptr(status), count, record_base,
+            _ptr(report), _stream(stream)))
+        return status[:count], report
+
     # ---- text front end: lines of "key<sep>value" -> descriptors -> kv.db image
     @staticmethod
     def _sep(separator) -> int:
@@ -987,14 +1027,15 @@ class Context:
 
     def text_pack(self, text, desc, count: int, partitions: int, part_sizes, approximate: bool = False,
                   nbytes: Optional[int] = None, image=None, addr=None, blob=None, off=None, value8=None, value_len=None,
-                  stream=None, block_size: Optional[int] = None) -> dict:
+                  stream=None, block_size: Optional[int] = None, want_image: bool = True) -> dict:
         """bsdb_dev_text_pack of the first `count` descriptors of text_split;
         with `block_size`, bsdb_dev_text_pack_blocked: the blocked layout in
         blocks of that many bytes (part_sizes multiples of 4096).
         The outputs are the caller's tensors or allocated here: image / blob /
         value_len uint8 at any address, addr / off / value8 int64.  Returns
         {"image", "run_bytes", "addr", "blob", "off", "value8", "value_len"},
-        each cut to what was written; run p is image[sum(run_bytes[:p]):][:run_bytes[p]]."""
+        each cut to what was written; run p is image[sum(run_bytes[:p]):][:run_bytes[p]].
+        ``want_image=False``: no image is written (the key blob and offsets alone)."""
         import numpy as np
         import torch
         if nbytes is None:
@@ -1003,7 +1044,7 @@ class Context:
         sizes = np.ascontiguousarray(part_sizes, np.uint64)
         if sizes.size != partitions:
             raise ValueError("one size per partition")
-        if image is None:
+        if image is None and want_image:
             image = torch.empty(text_image_max(nbytes, partitions, 0 if block_size is None else 1, block_size or 0),
                                 dtype=torch.uint8, device=dev)
         if blob is None:
@@ -1021,14 +1062,14 @@ class Context:
         runs = np.zeros(partitions, np.uint64)
         blob_bytes = C.c_uint64()
         head = (self._h, _ptr(text), nbytes, _ptr(desc[0]), _ptr(desc[1]), _ptr(desc[2]), _ptr(desc[3]), count, partitions)
-        tail = (sizes.ctypes.data, _ptr(image), image.numel(), runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(),
+        tail = (sizes.ctypes.data, _ptr(image) if want_image else None, image.numel() if want_image else 0, runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(),
                 _ptr(off), C.byref(blob_bytes), _ptr(value8) if approximate else None,
                 _ptr(value_len) if approximate else None, _stream(stream))
         if block_size is None:
             _check("bsdb_dev_text_pack", lib().bsdb_dev_text_pack(*head, *tail))
         else:
             _check("bsdb_dev_text_pack_blocked", lib().bsdb_dev_text_pack_blocked(*head, block_size, *tail))
-        return {"image": image[: int(runs.sum())], "run_bytes": [int(x) for x in runs], "addr": addr[:count],
+        return {"image": image[: int(runs.sum())] if want_image else None, "run_bytes": [int(x) for x in runs], "addr": addr[:count],
                 "blob": blob[: blob_bytes.value], "off": off[: count + 1],
                 "value8": value8[:count] if approximate else None, "value_len": value_len[:count] if approximate else None}
 
@@ -1255,6 +1296,11 @@ def _get_report(report) -> dict:
     return {k: int(v) for k, v in zip(GET_FIELDS, report)}
 
 
+def _check_report(report) -> dict:
+    """The check report's words as a dict (CHECK_FIELDS, the header's order); words taken as unsigned."""
+    return {k: int(v) & CHECK_NONE for k, v in zip(CHECK_FIELDS, report)}
+
+
 class Database:
     """``bsdb_db``: a finished database resident on one device; batched gets
     key -> value (SyncReader.getAsBytes for a batch).  Borrows its Mph."""
@@ -1324,6 +1370,31 @@ class Database:
         blob_np, off_np, nq = Context._var_host_args(blob_np, off_np)
         return self._get("bsdb_db_get_var", lambda cap, v, o, s, r: lib().bsdb_db_get_var(
             self._h, blob_np.ctypes.data, off_np.ctypes.data, nq, cap, v, o, s, r), nq, value_cap)
+
+    def check_text(self, paths, separator=" ", bad_cap: int = 16) -> dict:
+        """bsdb_db_check_text: the files of ``key<sep>value`` lines against
+        this database, every record's key -> value compared on the device.
+        Returns {"text": the split's report (TEXT_FIELDS), "check": the
+        check's (CHECK_FIELDS), "bad": up to bad_cap (path, file offset of the
+        record's key, status) of the records that are not OK in input order,
+        "n_bad": how many there are, "ok": every record is OK}.  It tells
+        whether the text is in the database, not the converse."""
+        import numpy as np
+        paths = [os.fspath(p) for p in paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        text = (C.c_uint64 * TEXT_WORDS)()
+        rep = (C.c_uint64 * CHECK_WORDS)()
+        cap = max(int(bad_cap), 0)
+        bfile, boff, bst = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint8)
+        n_bad = C.c_uint64()
+        rc = lib().bsdb_db_check_text(self._h, arr, len(paths), Context._sep(separator), text, rep, cap, bfile.ctypes.data,
+                                      boff.ctypes.data, bst.ctypes.data, C.byref(n_bad))
+        if rc not in (BSDB_OK, BSDB_EVERIFY):
+            _check("bsdb_db_check_text", rc)
+        held = min(cap, n_bad.value)
+        return {"text": {k: int(v) for k, v in zip(TEXT_FIELDS, text)}, "check": _check_report(rep),
+                "bad": [(paths[int(f)], int(o), int(s)) for f, o, s in zip(bfile[:held], boff[:held], bst[:held])],
+                "n_bad": int(n_bad.value), "ok": rc == BSDB_OK}
 
 
 class Builder:

@@ -272,7 +272,8 @@ int bsdb_fused_status(bsdb_ctx *ctx, uint64_t *launches, uint64_t *timeouts);
 /* Live per-kernel timing with HIP events recorded on the launch stream around
  * every pass-1 (hash+partition) and pass-2 (partition histogram) launch.
  * bsdb_profile_read synchronises those events and returns, for `kind`
- * (0 = pass 1, 1 = pass 2, 2 = edge-offset scan), the summed milliseconds, the
+ * (0 = pass 1, 1 = pass 2, 2 = edge-offset scan, 3 = the value compare of
+ * bsdb_dev_db_check, k_check_values alone), the summed milliseconds, the
  * number of launches and the keys they processed; then clears that kind. */
 int bsdb_set_profiling(bsdb_ctx *ctx, int enable);
 int bsdb_profile_read(bsdb_ctx *ctx, int kind, double *total_ms, uint64_t *launches, uint64_t *keys);
@@ -947,6 +948,74 @@ int bsdb_text_build_layout(bsdb_ctx *ctx, const char *const *paths, int nfiles, 
                            int partitions, int format, uint32_t block_size, uint32_t width, int approximate,
                            const char *index_path, const char *index_a_path, uint64_t *report /* BSDB_TEXT_WORDS */,
                            bsdb_mph **out);
+
+/* ---- a database checked against text input: key -> value compare ------------
+ * What the reference's Builder does with -v (tools/Builder.java:184-228): the
+ * input is read a second time, getAsBytes(key) is called for every record and
+ * the bytes it returns are compared with the value in the text.  Here, for a
+ * chunk of text on the device: the split gives the records, bsdb_dev_db_locate_var
+ * gives, per key, where the resident database's value lies, and the check
+ * compares the text's value bytes with the image's in place.  No value is
+ * gathered or written.  (bsdb_kv_verify_index walks the kv.db files and never
+ * reads the text: a record the split dropped, or a value taken from the wrong
+ * line, passes it.)
+ *
+ * Every record gets a status byte; the get's codes are kept:
+ *   0 OK                      found, the same length, the same bytes
+ *   1 BSDB_GET_REJECTED, 2 BSDB_GET_KEY_MISMATCH, 3 BSDB_GET_BAD_ADDR   as for the get
+ *   4 BSDB_CHECK_VALUE_LEN    found, the database's value has another length
+ *   5 BSDB_CHECK_VALUE_BYTES  found, the same length, some byte differs
+ * Approximate mode (the db holds index_a.db): the slot's 8 bytes are compared
+ * with the value head the text front end stores for the text's value (its first
+ * min(vLen, 8) bytes, the rest 0); there is no length status, and the false
+ * positive of an absent key shows up as VALUE_BYTES (or, when the slot happens
+ * to hold the same head, as OK).
+ * The report is uint64_t[BSDB_CHECK_WORDS], ACCUMULATED by the dev_ call:
+ *   [0] records   [1] ok   [2] rejected   [3] key_mismatch   [4] bad_addr
+ *   [5] value_len   [6] value_bytes
+ *   [7] first_bad: the smallest input-order index of a record that is not OK,
+ *       UINT64_MAX when there is none;   [0] == [1] + ... + [6].
+ *
+ * bsdb_dev_db_check: d_text (16-byte aligned, text_bytes < 2^32) is the chunk,
+ *   d_vpos / d_vlen the `count` kept records' value descriptors from
+ *   bsdb_dev_text_split, d_src / d_dbvlen / d_status what bsdb_dev_db_locate_var
+ *   returned for their keys (the key blob: bsdb_dev_text_pack).  d_status comes
+ *   in as locate's and goes out as the check's (a byte that is none of the get's
+ *   codes counts as BAD_ADDR).  d_report (8-byte aligned) is zeroed by the caller
+ *   with [7] = UINT64_MAX, and accumulates; record_base is the input-order index
+ *   of record 0, so [7] is global over the caller's chunks.  Descriptors,
+ *   positions and lengths are data: no byte outside the text and the image is
+ *   read, and a database length over 65 535 (none a record can have) is
+ *   VALUE_LEN.  The workspace is the context's.  Asynchronous.  BSDB_EINVAL before
+ *   any device call for null or misaligned arguments or text_bytes >= 2^32.
+ * bsdb_db_check_text: every file of paths[0 .. nfiles) is read a chunk at a
+ *   time exactly as bsdb_text_build reads it (the same cut rule, and
+ *   bsdb_text_set_chunk of the db's context; the chunk is halved until its
+ *   footprint fits half of the device memory that is free beside the resident
+ *   database), split, its keys packed, located and checked.  text_report is the
+ *   split's (BSDB_TEXT_WORDS), check_report the check's.  The records that are
+ *   not OK are appended in input order to h_bad_file (the index into paths),
+ *   h_bad_offset (the file offset of the first byte of the record's key) and
+ *   h_bad_status until bad_cap entries are held; *n_bad counts all of them.
+ *   Returns BSDB_OK when every record is OK, BSDB_EVERIFY with all outputs filled
+ *   when one is not, BSDB_E2BIG for a line longer than a chunk, BSDB_EFILE for a
+ *   file that cannot be read, BSDB_EINVAL for bad arguments (before any device
+ *   call) or a db whose MPHF was freed.  The empty input is BSDB_OK with all
+ *   counts 0.  It tells whether every record of the text is in the database, not
+ *   the converse: compare [1] with bsdb_db_info's n for that.
+ * Out of scope: compressed kv.db, a database that does not fit the device beside
+ * a chunk of text, overlapping the file reads with the device work.
+ * ------------------------------------------------------------------------- */
+#define BSDB_CHECK_WORDS 8
+#define BSDB_CHECK_VALUE_LEN 4
+#define BSDB_CHECK_VALUE_BYTES 5
+int bsdb_dev_db_check(bsdb_db *db, const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_vpos,
+                      const uint32_t *d_vlen, const uint64_t *d_src, const uint32_t *d_dbvlen, uint8_t *d_status,
+                      uint64_t count, uint64_t record_base, uint64_t *d_report, void *stream);
+int bsdb_db_check_text(bsdb_db *db, const char *const *paths, int nfiles, int separator,
+                       uint64_t *text_report /* BSDB_TEXT_WORDS */, uint64_t *check_report /* BSDB_CHECK_WORDS */,
+                       uint64_t bad_cap, uint32_t *h_bad_file, uint64_t *h_bad_offset, uint8_t *h_bad_status,
+                       uint64_t *n_bad);
 
 #ifdef __cplusplus
 }
