@@ -11,7 +11,9 @@
 // (batched get of a resident database, with its plan get_plan.hpp),
 // capi_text.hip (text lines into records, kv.db files in the compact or the
 // blocked layout and a database, with its plan text_plan.hpp), capi_check.hip
-// (a database checked against text input, with its plan check_plan.hpp).
+// (a database checked against text input, with its plan check_plan.hpp),
+// capi_dump.hip (a resident database enumerated by slot, with its plan
+// dump_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -55,6 +57,7 @@
 #include "text_kernels.hip"
 #include "text_blocked_kernels.hip"
 #include "check_kernels.hip"
+#include "dump_kernels.hip"
 
 using namespace bsdb;
 
@@ -1054,3 +1057,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_get.hip"
 #include "capi_text.hip"
 #include "capi_check.hip"
+#include "capi_dump.hip"

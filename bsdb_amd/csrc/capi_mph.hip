@@ -37,6 +37,7 @@ struct bsdb_db {
     uint32_t block_size = 0;
     bool approx = false;
     uint64_t n = 0, batch = 0;            // slots; the host forms' chunk (0 = default)
+    uint64_t text_chunk = 0;              // bsdb_db_set_text_chunk: text bytes of one step of bsdb_db_dump_text (0 = default)
     uint64_t image_bytes = 0;             // exact: the partitions; approximate: index_a.db
     uint8_t *d_image = nullptr;
     uint64_t *d_index = nullptr;          // exact: n big-endian addresses

@@ -48,6 +48,31 @@ struct GetArgs {
     unsigned long long *out;  // the report, GW_WORDS
 };
 
+// The record an index.db slot names (`addr`: the slot's word, byte-swapped):
+// its address decoded and bounds-tested (get_decode), its 3-byte header read,
+// and the whole record tested against its container's end.  !ok is
+// BSDB_GET_BAD_ADDR.  The key is image bytes [p + 3, p + 3 + kl), the value the
+// vb bytes after it; every read of them takes `lim` as its limit.
+// k_get_locate and k_db_records (dump_kernels.hip) both start here.
+struct GetSlot {
+    bool ok;
+    uint64_t p, lim;  // the record's and its container's end's byte position in the image
+    uint32_t kl, vb;  // BaseKVReader.java:19-20
+};
+
+__device__ __forceinline__ GetSlot get_slot(const GetDb &db, uint64_t addr) {
+    GetSlot s = {false, 0, 0, 0, 0};
+    const GetRecord rec = get_decode(addr, db.format, db.size, db.partitions);
+    if (!rec.ok) return s;
+    const uint64_t pb = db.base[rec.part];
+    s.lim = pb + rec.limit, s.p = pb + rec.pos;  // p + 3 <= lim <= image_bytes
+    const uint64_t h = sel_gload64(db.image, s.lim, s.p);
+    s.kl = (uint32_t)(h & 0xFF);
+    s.vb = (uint32_t)((h >> 8) & 0xFF) << 8 | (uint32_t)((h >> 16) & 0xFF);
+    s.ok = s.p + 3 + s.kl + s.vb <= s.lim;
+    return s;
+}
+
 // KIND as verify_records: 0 13-byte keys, 1 fixed key_len, 2 variable length.
 // One query per lane; the loop is uniform per wave so the ballots see all lanes.
 template <int KIND>
@@ -86,24 +111,19 @@ __device__ __forceinline__ void get_locate(const MphView &v, const GetDb &db, co
                 vl = 8;
             } else if (r >= 0) {
                 st = GET_BAD_ADDR;
-                const GetRecord rec = get_decode(__builtin_bswap64(db.index[r]), db.format, db.size, db.partitions);
+                const GetSlot rec = get_slot(db, __builtin_bswap64(db.index[r]));
                 if (rec.ok) {
-                    const uint64_t pb = db.base[rec.part];
-                    const uint64_t lim = pb + rec.limit, p = pb + rec.pos;  // p + 3 <= lim <= image_bytes
-                    const uint64_t h = sel_gload64(db.image, lim, p);
-                    const uint32_t kl = (uint32_t)(h & 0xFF);               // BaseKVReader.java:19-20
-                    const uint32_t vb = (uint32_t)((h >> 8) & 0xFF) << 8 | (uint32_t)((h >> 16) & 0xFF);
-                    if (p + 3 + kl + vb <= lim) {
-                        bool same = kl == klen;                              // BaseKVReader.java:66-69
-                        for (uint32_t o = 0; same && o < kl; o += 8) {
-                            const uint32_t k = kl - o < 8 ? kl - o : 8;
-                            same = ((sel_gload64(db.image, lim, p + 3 + o) ^ rdk(o)) & low_bytes_mask(k)) == 0;
-                        }
-                        st = same ? GET_FOUND : GET_KEY_MISMATCH;
-                        if (same) {
-                            src = p + 3 + kl;
-                            vl = vb;
-                        }
+                    const uint64_t lim = rec.lim, p = rec.p;
+                    const uint32_t kl = rec.kl;
+                    bool same = kl == klen;                              // BaseKVReader.java:66-69
+                    for (uint32_t o = 0; same && o < kl; o += 8) {
+                        const uint32_t k = kl - o < 8 ? kl - o : 8;
+                        same = ((sel_gload64(db.image, lim, p + 3 + o) ^ rdk(o)) & low_bytes_mask(k)) == 0;
+                    }
+                    st = same ? GET_FOUND : GET_KEY_MISMATCH;
+                    if (same) {
+                        src = p + 3 + kl;
+                        vl = rec.vb;
                     }
                 }
             }

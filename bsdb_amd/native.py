@@ -162,6 +162,12 @@ SIGNATURES = [
                                     C.c_char_p, _vp, C.POINTER(_vp)]),
     ("bsdb_dev_db_check", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     ("bsdb_db_check_text", _i, [_vp, C.POINTER(C.c_char_p), _i, _i, _vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
+    ("bsdb_dev_db_records", _i, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_dump_lengths", _i, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_dump_text", _i, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _u64, _vp, _u64, _vp, _vp]),
+    ("bsdb_db_set_text_chunk", _i, [_vp, _u64]),
+    ("bsdb_db_scan", _i, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_db_dump_text", _i, [_vp, C.c_char_p, _i, _u64, _u64, _i, _vp]),
 ]
 
 TEXT_WORDS = 10
@@ -184,6 +190,13 @@ CHECK_FIELDS = ("records", "ok", "rejected", "key_mismatch", "bad_addr", "value_
 CHECK_OK, CHECK_VALUE_LEN, CHECK_VALUE_BYTES = 0, 4, 5  # a record's status byte; 1 .. 3 are the get's
 CHECK_NONE = (1 << 64) - 1  # first_bad when every record is OK
 CHECK_STATUS_NAMES = CHECK_FIELDS[1:7]  # a status byte's name is its counter's
+
+SCAN_WORDS = 8
+# the scan report's words in the header's order (uint64_t[BSDB_SCAN_WORDS])
+SCAN_FIELDS = ("slots", "ok", "bad_addr", "not_text", "key_bytes", "value_bytes", "text_bytes", "first_bad")
+SCAN_OK, SCAN_BAD_ADDR, SCAN_NOT_TEXT = 0, 1, 2  # a slot's status byte
+SCAN_NONE = (1 << 64) - 1  # first_bad when every slot is OK
+DUMP_MAX_LINE = 255 + 65535 + 2  # the smallest text-chunk cap: the longest line
 
 BSDB_EVERIFY = -74
 VERIFY_WORDS = 8
@@ -368,7 +381,7 @@ class Context:
         return a.value, b.value
 
     # ---- live per-kernel timing (HIP events on the launch stream)
-    PASS1, PASS2, SCAN, CHECK_VALUES = 0, 1, 2, 3
+    PASS1, PASS2, SCAN, CHECK_VALUES, DUMP_TEXT = 0, 1, 2, 3, 4
 
     def set_profiling(self, on: bool):
         _check("bsdb_set_profiling", lib().bsdb_set_profiling(self._h, 1 if on else 0))
@@ -994,6 +1007,83 @@ class Context:
             _ptr(report), _stream(stream)))
         return status[:count], report
 
+    # ---- a resident database enumerated by slot: records -> lengths -> text
+    @staticmethod
+    def scan_report(device):
+        """A fresh device report for db_records / db_dump_text: int64[SCAN_WORDS], zero with first_bad = UINT64_MAX (-1)."""
+        import torch
+        report = torch.zeros(SCAN_WORDS, dtype=torch.int64, device=device)
+        report[SCAN_WORDS - 1] = -1
+        return report
+
+    def db_records(self, db: "Database", first: int = 0, count: Optional[int] = None, report=None, stream=None):
+        """bsdb_dev_db_records: slots [first, first + count) of the resident
+        database as (ksrc, klen, vsrc, vlen, status, report) tensors: the
+        byte positions (int64) and lengths (int32) of every record's key and
+        value in the image, a status byte, and the report
+        (Context.scan_report, made here when not given; it accumulates).
+        Packed keys: ``db_gather(db, ksrc, edge_offsets(klen))``; values alike."""
+        import torch
+        if count is None:
+            count = db.info()["n"] - first
+        dev = torch.device(f"cuda:{self.device}") if report is None else report.device
+        if report is None:
+            report = self.scan_report(dev)
+        k = max(count, 1)
+        ksrc, vsrc = (torch.empty(k, dtype=torch.int64, device=dev) for _ in range(2))
+        klen, vlen = (torch.empty(k, dtype=torch.int32, device=dev) for _ in range(2))
+        status = torch.empty(k, dtype=torch.uint8, device=dev)
+        _check("bsdb_dev_db_records", lib().bsdb_dev_db_records(
+            db._h, first, count, _ptr(ksrc), _ptr(klen), _ptr(vsrc), _ptr(vlen), _ptr(status), _ptr(report), _stream(stream)))
+        return ksrc[:count], klen[:count], vsrc[:count], vlen[:count], status[:count], report
+
+    def db_dump_lengths(self, db: "Database", klen, vlen, status, stream=None):
+        """bsdb_dev_db_dump_lengths: (llen int32[count], loff int64[count + 1]):
+        every record's line length and their exclusive scan; `status` gets
+        the length part of NOT_TEXT in place."""
+        import torch
+        count = status.numel()
+        llen = torch.empty(max(count, 1), dtype=torch.int32, device=status.device)
+        loff = torch.empty(count + 1, dtype=torch.int64, device=status.device)
+        if klen.dtype != torch.int32 or vlen.dtype != torch.int32 or status.dtype != torch.uint8 or min(klen.numel(), vlen.numel()) < count:
+            raise ValueError("klen / vlen int32[count], status uint8[count]")
+        _check("bsdb_dev_db_dump_lengths", lib().bsdb_dev_db_dump_lengths(
+            db._h, count, _ptr(klen), _ptr(vlen), _ptr(status), _ptr(llen), _ptr(loff), _stream(stream)))
+        return llen[:count], loff
+
+    def db_dump_text(self, db: "Database", ksrc, klen, vsrc, vlen, status, separator=" ", first: int = 0, text=None, llen=None,
+                     loff=None, text_bytes: Optional[int] = None, report=None, stream=None):
+        """bsdb_dev_db_dump_text: the records' lines ``key<sep>value\n`` in
+        slot order as a uint8 tensor, (text, status, report).  Without llen /
+        loff it runs db_dump_lengths first and reads the text's length back
+        (which synchronises, as does reading loff[count] when text_bytes is not
+        given).  `text`: a uint8 tensor (any alignment) of at least
+        loff[count] bytes; `status` (db_records') gets NOT_TEXT in
+        place; `report` as for db_records, a fresh one when not given; `first`
+        is the slot of record 0 (for the report's first_bad)."""
+        import torch
+        count = status.numel()
+        if llen is None or loff is None:
+            llen, loff = self.db_dump_lengths(db, klen, vlen, status, stream=stream)
+        if text_bytes is None:
+            text_bytes = int(loff[count])
+        if text is None:
+            text = torch.empty(max(text_bytes, 1), dtype=torch.uint8, device=status.device)
+        elif text.dtype != torch.uint8 or text.numel() < text_bytes or not text.is_contiguous():
+            raise ValueError("text holds fewer than loff[count] contiguous bytes")
+        if report is None:
+            report = self.scan_report(status.device)
+        if (ksrc.dtype != torch.int64 or vsrc.dtype != torch.int64 or klen.dtype != torch.int32 or vlen.dtype != torch.int32
+                or llen.dtype != torch.int32 or loff.dtype != torch.int64 or status.dtype != torch.uint8
+                or report.dtype != torch.int64 or report.numel() < SCAN_WORDS or loff.numel() < count + 1
+                or min(ksrc.numel(), vsrc.numel(), klen.numel(), vlen.numel(), llen.numel()) < count):
+            raise ValueError("ksrc / vsrc int64[count], klen / vlen / llen int32[count], loff int64[count + 1], "
+                             "status uint8[count], report int64[SCAN_WORDS]")
+        _check("bsdb_dev_db_dump_text", lib().bsdb_dev_db_dump_text(
+            db._h, count, _ptr(ksrc), _ptr(klen), _ptr(vsrc), _ptr(vlen), _ptr(llen), _ptr(loff), self._sep(separator), _ptr(text),
+            text_bytes, _ptr(status), first, _ptr(report), _stream(stream)))
+        return text[:text_bytes], status, report
+
     # ---- text front end: lines of "key<sep>value" -> descriptors -> kv.db image
     @staticmethod
     def _sep(separator) -> int:
@@ -1296,6 +1386,11 @@ def _get_report(report) -> dict:
     return {k: int(v) for k, v in zip(GET_FIELDS, report)}
 
 
+def _scan_report(report) -> dict:
+    """The scan report's words as a dict (SCAN_FIELDS, the header's order); words taken as unsigned."""
+    return {k: int(v) & SCAN_NONE for k, v in zip(SCAN_FIELDS, report)}
+
+
 def _check_report(report) -> dict:
     """The check report's words as a dict (CHECK_FIELDS, the header's order); words taken as unsigned."""
     return {k: int(v) & CHECK_NONE for k, v in zip(CHECK_FIELDS, report)}
@@ -1395,6 +1490,50 @@ class Database:
         return {"text": {k: int(v) for k, v in zip(TEXT_FIELDS, text)}, "check": _check_report(rep),
                 "bad": [(paths[int(f)], int(o), int(s)) for f, o, s in zip(bfile[:held], boff[:held], bst[:held])],
                 "n_bad": int(n_bad.value), "ok": rc == BSDB_OK}
+
+    # ---- what the database holds, by slot
+    def set_text_chunk(self, nbytes: int = 0):
+        """Text bytes of one step of dump_text (0 = default, 256 MiB; at least DUMP_MAX_LINE); results do not depend on it."""
+        _check("bsdb_db_set_text_chunk", lib().bsdb_db_set_text_chunk(self._h, nbytes))
+
+    def items(self, first: int = 0, count: Optional[int] = None, key_cap: Optional[int] = None,
+              value_cap: Optional[int] = None) -> dict:
+        """bsdb_db_scan: the records of slots [first, first + count) (to the
+        last slot when count is None) in slot order: {"keys" u8, "koff"
+        u64[count + 1], "values" u8, "voff" u64[count + 1], "status"
+        u8[count], "report" dict (SCAN_FIELDS)}; key i is
+        keys[koff[i]:koff[i + 1]], value i alike; a BAD_ADDR slot has neither.
+        Once more with the reported sizes on BSDB_E2BIG."""
+        import numpy as np
+        if count is None:
+            count = self.info()["n"] - first
+        status = np.zeros(max(count, 1), np.uint8)
+        koff, voff = np.zeros(count + 1, np.uint64), np.zeros(count + 1, np.uint64)
+        report = np.zeros(SCAN_WORDS, np.uint64)
+        kcap = 16 * count if key_cap is None else key_cap
+        vcap = 64 * count if value_cap is None else value_cap
+        for _ in range(2):
+            keys, values = np.zeros(max(kcap, 1), np.uint8), np.zeros(max(vcap, 1), np.uint8)
+            rc = lib().bsdb_db_scan(self._h, first, count, kcap, vcap, keys.ctypes.data, koff.ctypes.data, values.ctypes.data,
+                                    voff.ctypes.data, status.ctypes.data, report.ctypes.data)
+            if rc != BSDB_E2BIG:
+                break
+            kcap, vcap = max(kcap, int(report[4])), max(vcap, int(report[5]))
+        _check("bsdb_db_scan", rc)
+        return {"keys": keys[: int(koff[count])], "koff": koff, "values": values[: int(voff[count])], "voff": voff,
+                "status": status[:count], "report": _scan_report(report)}
+
+    def dump_text(self, path, separator=" ", first: int = 0, count: Optional[int] = None, append: bool = False) -> dict:
+        """bsdb_db_dump_text: the lines ``key<sep>value\n`` of slots [first,
+        first + count) to the file `path` (appended to it when `append`), in
+        slot order.  Returns the report (SCAN_FIELDS): a BAD_ADDR slot wrote
+        nothing, a NOT_TEXT record was written raw and does not read back."""
+        if count is None:
+            count = self.info()["n"] - first
+        report = (C.c_uint64 * SCAN_WORDS)()
+        _check("bsdb_db_dump_text", lib().bsdb_db_dump_text(
+            self._h, os.fsencode(os.fspath(path)), Context._sep(separator), first, count, 1 if append else 0, report))
+        return _scan_report(report)
 
 
 class Builder:

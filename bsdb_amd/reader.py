@@ -11,6 +11,15 @@ told from a present one by the key compare alone, and in approximate mode
 every absent key whose rank is below n is a false positive, as for the
 reference without checksum bits).  Compressed kv.db files are out of scope, as
 for the scan.  Every lookup runs in the gfx950 kernels: no CPU fallback.
+
+An exact database also lists itself, by slot (bsdb_db_scan, bsdb_db_dump_text):
+``items()`` yields its (key, value) pairs, ``dump_text(path)`` writes them as
+``key<sep>value`` lines that ``BSDBWriter.build_text`` reads back, and
+
+    python -m bsdb_amd.reader --dump out.txt -d DB [-s SEP] [--first N --count M]
+
+does the latter from the command line: exit status 0 when every slot is OK, 2
+when a slot's address names no record or a record's line does not read back.
 """
 from __future__ import annotations
 
@@ -19,7 +28,7 @@ from typing import Optional
 
 import numpy as np
 
-from .native import GET_FOUND, Context, Database
+from .native import GET_FOUND, SCAN_NONE, SCAN_OK, Context, Database
 
 
 def _read_config(path: str) -> dict:
@@ -71,6 +80,23 @@ class BSDBReader:
         r = self.get_batch(np.frombuffer(bytes(key), np.uint8), np.array([0, len(key)], np.uint64))
         return r["values"].tobytes() if r["status"][0] == GET_FOUND else None
 
+    def items(self, batch: int = 1 << 20, first: int = 0, count: Optional[int] = None):
+        """The database's (key, value) pairs as bytes, in slot order, `batch`
+        slots a call of Database.items; a slot whose address names no record
+        is skipped."""
+        end = self.db.info()["n"] if count is None else first + count
+        for r0 in range(first, end, max(1, batch)):
+            r = self.db.items(r0, min(batch, end - r0))
+            keys, values = r["keys"].tobytes(), r["values"].tobytes()
+            koff, voff = r["koff"].tolist(), r["voff"].tolist()
+            for i, st in enumerate(r["status"].tolist()):
+                if st == SCAN_OK:
+                    yield keys[koff[i]: koff[i + 1]], values[voff[i]: voff[i + 1]]
+
+    def dump_text(self, path, separator=" ", first: int = 0, count: Optional[int] = None, append: bool = False) -> dict:
+        """Database.dump_text: the ``key<sep>value`` lines of the slots to `path`; returns the report."""
+        return self.db.dump_text(path, separator, first, count, append)
+
     def close(self):
         for o in (self.db, self.mph, self.ctx):
             if o is not None:
@@ -82,3 +108,25 @@ class BSDBReader:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m bsdb_amd.reader", description="dump a database directory as key<sep>value lines")
+    ap.add_argument("--dump", required=True, metavar="OUT", help="the text file to write")
+    ap.add_argument("-d", "--db", required=True, help="the database directory")
+    ap.add_argument("-s", "--separator", default=" ", help="the one-byte field separator (default: a space)")
+    ap.add_argument("--first", type=int, default=0, help="the first slot (default 0)")
+    ap.add_argument("--count", type=int, default=None, help="slots to dump (default: to the last)")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    with BSDBReader(a.db, approximate=False, device=a.device) as rd:
+        rep = rd.dump_text(a.dump, a.separator, a.first, a.count)
+    first_bad = "none" if rep["first_bad"] == SCAN_NONE else rep["first_bad"]
+    print(f"slots {rep['slots']}  ok {rep['ok']}  bad_addr {rep['bad_addr']}  not_text {rep['not_text']}  "
+          f"text_bytes {rep['text_bytes']}  first_bad {first_bad}")
+    return 0 if rep["ok"] == rep["slots"] else 2
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -273,7 +273,8 @@ int bsdb_fused_status(bsdb_ctx *ctx, uint64_t *launches, uint64_t *timeouts);
  * every pass-1 (hash+partition) and pass-2 (partition histogram) launch.
  * bsdb_profile_read synchronises those events and returns, for `kind`
  * (0 = pass 1, 1 = pass 2, 2 = edge-offset scan, 3 = the value compare of
- * bsdb_dev_db_check, k_check_values alone), the summed milliseconds, the
+ * bsdb_dev_db_check, k_check_values alone, 4 = the text kernel of
+ * bsdb_dev_db_dump_text, k_dump_text alone), the summed milliseconds, the
  * number of launches and the keys they processed; then clears that kind. */
 int bsdb_set_profiling(bsdb_ctx *ctx, int enable);
 int bsdb_profile_read(bsdb_ctx *ctx, int kind, double *total_ms, uint64_t *launches, uint64_t *keys);
@@ -1016,6 +1017,99 @@ int bsdb_db_check_text(bsdb_db *db, const char *const *paths, int nfiles, int se
                        uint64_t *text_report /* BSDB_TEXT_WORDS */, uint64_t *check_report /* BSDB_CHECK_WORDS */,
                        uint64_t bad_cap, uint32_t *h_bad_file, uint64_t *h_bad_offset, uint8_t *h_bad_status,
                        uint64_t *n_bad);
+
+/* ---- a resident database enumerated by slot: records, items, a text dump ----
+ * index.db is n slots and every slot is the address of one record, so a
+ * resident database lists itself: slot r (the rank the MPHF gives r's key) ->
+ * address -> 3-byte header -> key and value.  No key is needed, nothing is
+ * hashed.  The order is slot order, rank 0 .. n - 1: deterministic for a given
+ * database, and any window [first, first + count) can be taken on its own.
+ * (The reference has no dump; KVWriter.forEach walks the files in file order
+ * for buildIndex.)  Exact mode only: an approximate database holds no records,
+ * and every call here returns BSDB_EINVAL for it.
+ *
+ * Every slot gets a status byte:
+ *   BSDB_SCAN_OK        the slot names a whole record
+ *   BSDB_SCAN_BAD_ADDR  its address does not (the rule of BSDB_GET_BAD_ADDR,
+ *                       the same function); both lengths and positions are 0,
+ *                       and it writes nothing to a text
+ *   BSDB_SCAN_NOT_TEXT  set only by the text calls: the record's line
+ *                       key<sep>value\n does not read back as that record
+ *                       through the text front end (bsdb_text_build): the key
+ *                       or the value is empty, the value is longer than
+ *                       32 510 bytes, or a key or value byte is the separator,
+ *                       0x0A or 0x0D.  Its bytes are written raw all the same;
+ *                       the report says the text cannot carry them, and the
+ *                       caller decides.
+ * The report is uint64_t[BSDB_SCAN_WORDS], ACCUMULATED by the dev_ calls into
+ * words the caller zeroed, with [7] = UINT64_MAX:
+ *   [0] slots   [1] ok   [2] bad_addr   [3] not_text   [0] == [1] + [2] + [3]
+ *   [4] key_bytes   [5] value_bytes   (of the slots that are not BAD_ADDR)
+ *   [6] text_bytes  (0 from bsdb_dev_db_records and bsdb_db_scan)
+ *   [7] first_bad: the lowest slot that is not OK, UINT64_MAX when there is none
+ * bsdb_dev_db_records and bsdb_dev_db_dump_text each fill a whole report for
+ * the records they see: give each its own, or the counts add up twice.
+ *
+ * bsdb_dev_db_records: for slot first + i, i < count: d_ksrc[i] / d_vsrc[i]
+ *   (u64, 8-byte aligned) the byte positions of key and value in the resident
+ *   image, d_klen[i] / d_vlen[i] (u32, so bsdb_dev_edge_offsets scans them),
+ *   d_status[i].  Packed keys and values need no further call of their own:
+ *   bsdb_dev_edge_offsets over d_klen (d_vlen), then bsdb_dev_db_gather with
+ *   d_ksrc (d_vsrc).  Asynchronous.
+ * bsdb_dev_db_dump_lengths: d_llen[i] = the bytes of record i's line (kLen + 1
+ *   + vLen + 1, 0 for BAD_ADDR), d_loff[count + 1] their exclusive scan;
+ *   d_status comes in as bsdb_dev_db_records' and goes out with the length
+ *   part of NOT_TEXT (a byte that is none of the codes counts as BAD_ADDR).
+ *   The caller reads d_loff[count], the text's length, before the next call
+ *   (as the get leaves its scan to the caller).  The workspace is the
+ *   context's.  Asynchronous.
+ * bsdb_dev_db_dump_text: the text_bytes = d_loff[count] bytes of the lines to
+ *   d_text (any alignment), the bytes' part of NOT_TEXT into d_status, then the
+ *   report; `first` is the slot of record 0, so [7] is a slot.  Descriptors and
+ *   offsets are data: no byte outside the image is read (a position past it
+ *   reads as 0), lengths are cut to what a header holds (255, 65 535), offsets
+ *   that are no scan leave zeros, and nothing is written outside [d_text,
+ *   d_text + text_bytes).  Asynchronous.
+ * bsdb_db_scan: the window's records in host memory, streamed in chunks of
+ *   bsdb_db_set_batch slots: h_keys / h_koff[count + 1] and h_values /
+ *   h_voff[count + 1] packed with offsets over the whole call, h_status[count].
+ *   Past key_cap or value_cap it goes on without gathering that side and
+ *   returns BSDB_E2BIG with offsets, status and report complete (report [4],
+ *   [5] are the sizes to come back with), as bsdb_db_get_* does.
+ * bsdb_db_dump_text: the window's lines to the file `path` (created;
+ *   truncated unless `append`), a chunk of slots at a time, each cut so that
+ *   its text stays under the cap of bsdb_db_set_text_chunk (0 = the default,
+ *   256 MiB; a cap below the longest line, 255 + 65 535 + 2 bytes, is
+ *   BSDB_EINVAL): never more than one such piece of text is held on either
+ *   side.  Returns BSDB_OK whatever the statuses: report [2], [3] and [7] say
+ *   whether the text carries the database.
+ * All: BSDB_EINVAL before any device call for null or misaligned arguments, a
+ *   bad separator (as for bsdb_text_build), first + count > n, an approximate
+ *   db or one whose MPHF was freed; count == 0 is BSDB_OK with an empty result;
+ *   BSDB_EFILE for a file that cannot be written.
+ * Out of scope: the diff of two databases, escaping NOT_TEXT records, other
+ * line terminators, compressed kv.db, a kv.db larger than device memory, and
+ * whether each slot is its own key's (bsdb_kv_verify_index: a dump presumes a
+ * verified database).
+ * ------------------------------------------------------------------------- */
+#define BSDB_SCAN_WORDS 8
+#define BSDB_SCAN_OK 0
+#define BSDB_SCAN_BAD_ADDR 1
+#define BSDB_SCAN_NOT_TEXT 2
+int bsdb_dev_db_records(bsdb_db *db, uint64_t first, uint64_t count, uint64_t *d_ksrc, uint32_t *d_klen,
+                        uint64_t *d_vsrc, uint32_t *d_vlen, uint8_t *d_status, uint64_t *d_report, void *stream);
+int bsdb_dev_db_dump_lengths(bsdb_db *db, uint64_t count, const uint32_t *d_klen, const uint32_t *d_vlen,
+                             uint8_t *d_status, uint32_t *d_llen, uint64_t *d_loff, void *stream);
+int bsdb_dev_db_dump_text(bsdb_db *db, uint64_t count, const uint64_t *d_ksrc, const uint32_t *d_klen,
+                          const uint64_t *d_vsrc, const uint32_t *d_vlen, const uint32_t *d_llen, const uint64_t *d_loff,
+                          int separator, uint8_t *d_text, uint64_t text_bytes, uint8_t *d_status, uint64_t first,
+                          uint64_t *d_report /* BSDB_SCAN_WORDS */, void *stream);
+int bsdb_db_set_text_chunk(bsdb_db *db, uint64_t bytes);
+int bsdb_db_scan(bsdb_db *db, uint64_t first, uint64_t count, uint64_t key_cap, uint64_t value_cap, uint8_t *h_keys,
+                 uint64_t *h_koff, uint8_t *h_values, uint64_t *h_voff, uint8_t *h_status,
+                 uint64_t *report /* BSDB_SCAN_WORDS */);
+int bsdb_db_dump_text(bsdb_db *db, const char *path, int separator, uint64_t first, uint64_t count, int append,
+                      uint64_t *report /* BSDB_SCAN_WORDS */);
 
 #ifdef __cplusplus
 }
