@@ -139,8 +139,9 @@ __device__ __forceinline__ uint64_t funnel64(uint32_t d0, uint32_t d1, uint32_t 
 __device__ __forceinline__ uint64_t sel_gload64(const uint8_t *base, uint64_t limit, uint64_t pos) {
     const uint64_t a = pos & ~3ULL;
     const uint32_t sh = (uint32_t)(pos & 3) * 8;
+    typedef uint32_t u32any __attribute__((aligned(1)));  // `base` may be any address (a key blob): one dword load all the same
     auto ld = [&](uint64_t x) -> uint32_t {
-        if (x + 4 <= limit) return *reinterpret_cast<const uint32_t *>(base + x);
+        if (x + 4 <= limit) return *reinterpret_cast<const u32any *>(base + x);
         uint32_t w = 0;
         for (int b = 0; b < 4; ++b)
             if (x + b < limit) w |= (uint32_t)base[x + b] << (8 * b);
@@ -202,10 +203,15 @@ __device__ __forceinline__ void short_end_w(W64 &h0, W64 &h1, W64 &h2, W64 &h3) 
 // 16-key loop -- and pass 1 at C4 ran 0.68 ms slower.  The asm form's price is
 // the `s_nop 0` the compiler puts after it where the next instruction reads
 // the sum, 35 of them per loop, which other waves fill.  DESIGN §4.1.)
+// Off the device (the host emulation of tests/hostwave) it is the plain add.
 __device__ __forceinline__ uint64_t add_u(uint64_t a, uint64_t b) {
+#if defined(__AMDGCN__)
     uint64_t r;
     asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
+#else
+    return a + b;
+#endif
 }
 template <int K>
 __device__ __forceinline__ uint64_t rotl_u(uint64_t x) {

@@ -23,97 +23,14 @@
 //              that are no scan), k_dump_text over text_bytes = loff[count]
 //              (or text_bytes=...) and k_dump_report; over the first stage's
 //              descriptors, or over ksrc= klen= vsrc= vlen= status= given
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <map>
-#include <sstream>
-#include <string>
-#include <vector>
+#include "host_check_util.hpp"
 
 #include "dump_kernels.hip"
 
 using namespace bsdb;
+using namespace hostcheck;
 
 namespace {
-
-constexpr uint8_t GUARD = 0xA5;
-constexpr size_t FENCE = 64;
-
-template <class T>
-struct Exact {
-    T *p = nullptr;
-    size_t n = 0;
-    explicit Exact(size_t n_) : n(n_) {
-        void *q = nullptr;
-        if (posix_memalign(&q, 16, n * sizeof(T))) abort();
-        p = (T *)q;
-    }
-    Exact(const std::vector<T> &v) : Exact(v.size()) {
-        if (n) memcpy(p, v.data(), n * sizeof(T));
-    }
-    Exact(const Exact &) = delete;
-    ~Exact() { free(p); }
-};
-
-template <class T>
-struct Guarded {
-    uint8_t *base = nullptr;
-    size_t n, lead, bytes;
-    Guarded(size_t n_, uint32_t mis) : n(n_), lead(FENCE + (mis & ~(uint32_t)(alignof(T) - 1))) {
-        bytes = lead + n_ * sizeof(T) + FENCE;
-        void *q = nullptr;
-        if (posix_memalign(&q, 16, bytes)) abort();
-        base = (uint8_t *)q;
-        memset(base, GUARD, bytes);
-    }
-    Guarded(const Guarded &) = delete;
-    ~Guarded() { free(base); }
-    T *view() { return (T *)(base + lead); }
-    void fill(const std::vector<T> &v) {
-        if (v.size()) memcpy(view(), v.data(), v.size() * sizeof(T));
-    }
-    bool intact() const {
-        for (size_t i = 0; i < lead; ++i)
-            if (base[i] != GUARD) return false;
-        for (size_t i = lead + n * sizeof(T); i < bytes; ++i)
-            if (base[i] != GUARD) return false;
-        return true;
-    }
-};
-
-struct Case {
-    std::map<std::string, std::string> kv;
-    bool has(const char *k) const { return kv.count(k) != 0; }
-    uint64_t num(const char *k, uint64_t dflt) const {
-        auto it = kv.find(k);
-        return it == kv.end() ? dflt : strtoull(it->second.c_str(), nullptr, 10);
-    }
-    template <class T>
-    std::vector<T> list(const char *k) const {
-        std::vector<T> out;
-        auto it = kv.find(k);
-        if (it == kv.end() || it->second.empty()) return out;
-        const char *s = it->second.c_str();
-        for (;;) {
-            char *end;
-            out.push_back((T)strtoull(s, &end, 10));
-            if (*end != ',') break;
-            s = end + 1;
-        }
-        return out;
-    }
-    std::vector<uint8_t> hex(const char *k) const {
-        std::vector<uint8_t> out;
-        auto it = kv.find(k);
-        if (it == kv.end()) return out;
-        const std::string &h = it->second;
-        auto nib = [](char c) { return (uint8_t)(c <= '9' ? c - '0' : c - 'a' + 10); };
-        for (size_t i = 0; i + 1 < h.size(); i += 2) out.push_back((uint8_t)(nib(h[i]) << 4 | nib(h[i + 1])));
-        return out;
-    }
-};
 
 template <class T>
 void print_list(const char *name, const T *p, size_t n) {

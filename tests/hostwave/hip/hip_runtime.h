@@ -74,8 +74,17 @@ struct alignas(8) uint2 {
 struct alignas(16) uint4 {
     uint32_t x, y, z, w;
 };
+// (A copy of an aggregate is a memcpy, at which UBSan does not look; these copy through a reference, so a 16-byte
+// load from an address that is no multiple of 16 -- fine for x86 and for the GPU alike -- is a report here.)
 struct alignas(16) ulonglong2 {
     unsigned long long x, y;
+    ulonglong2() = default;
+    constexpr ulonglong2(unsigned long long x_, unsigned long long y_) : x(x_), y(y_) {}
+    constexpr ulonglong2(const ulonglong2 &o) : x(o.x), y(o.y) {}
+    constexpr ulonglong2 &operator=(const ulonglong2 &o) {
+        x = o.x, y = o.y;
+        return *this;
+    }
 };
 inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 inline ulonglong2 make_ulonglong2(unsigned long long x, unsigned long long y) { return ulonglong2{x, y}; }

@@ -21,111 +21,15 @@
 //   pack_blocked  text_pack_impl + text_place_blocked (capi_text.hip)
 //   split         text_split_impl (capi_text.hip)
 // with a plain prefix sum where the library runs k_scan_* (edge_offsets_impl).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <map>
-#include <sstream>
-#include <string>
-#include <vector>
+#include "host_check_util.hpp"
 
 #include "get_kernels.hip"
 #include "text_blocked_kernels.hip"
 
 using namespace bsdb;
+using namespace hostcheck;
 
 namespace {
-
-constexpr uint8_t GUARD = 0xA5;
-constexpr size_t FENCE = 64;  // guard bytes on either side of an output (a multiple of 16)
-
-// n elements of T in an allocation of exactly n * sizeof(T) bytes, 16-byte aligned
-template <class T>
-struct Exact {
-    T *p = nullptr;
-    size_t n = 0;
-    explicit Exact(size_t n_) : n(n_) {
-        void *q = nullptr;
-        if (posix_memalign(&q, 16, n * sizeof(T))) abort();
-        p = (T *)q;
-    }
-    Exact(const std::vector<T> &v) : Exact(v.size()) {
-        if (n) memcpy(p, v.data(), n * sizeof(T));
-    }
-    Exact(const Exact &) = delete;
-    ~Exact() { free(p); }
-    T &operator[](size_t i) { return p[i]; }
-};
-
-// n elements of T at `mis` bytes past a 16-byte aligned address, between guard bytes
-template <class T>
-struct Guarded {
-    uint8_t *base = nullptr;
-    size_t n, lead, bytes;
-    Guarded(size_t n_, uint32_t mis) : n(n_), lead(FENCE + mis), bytes(FENCE + mis + n_ * sizeof(T) + FENCE) {
-        void *q = nullptr;
-        if (posix_memalign(&q, 16, bytes)) abort();
-        base = (uint8_t *)q;
-        memset(base, GUARD, bytes);
-    }
-    Guarded(const Guarded &) = delete;
-    ~Guarded() { free(base); }
-    T *view() { return (T *)(base + lead); }
-    bool intact() const {
-        for (size_t i = 0; i < lead; ++i)
-            if (base[i] != GUARD) return false;
-        for (size_t i = lead + n * sizeof(T); i < bytes; ++i)
-            if (base[i] != GUARD) return false;
-        return true;
-    }
-};
-
-struct Case {
-    std::map<std::string, std::string> kv;
-    bool has(const char *k) const { return kv.count(k) != 0; }
-    uint64_t num(const char *k, uint64_t dflt) const {
-        auto it = kv.find(k);
-        return it == kv.end() ? dflt : strtoull(it->second.c_str(), nullptr, 10);
-    }
-    template <class T>
-    std::vector<T> list(const char *k) const {
-        std::vector<T> out;
-        auto it = kv.find(k);
-        if (it == kv.end() || it->second.empty()) return out;
-        const char *s = it->second.c_str();
-        for (;;) {
-            char *end;
-            out.push_back((T)strtoull(s, &end, 10));
-            if (*end != ',') break;
-            s = end + 1;
-        }
-        return out;
-    }
-    std::vector<uint8_t> hex(const char *k) const {
-        std::vector<uint8_t> out;
-        auto it = kv.find(k);
-        if (it == kv.end()) return out;
-        const std::string &h = it->second;
-        auto nib = [](char c) { return (uint8_t)(c <= '9' ? c - '0' : c - 'a' + 10); };
-        for (size_t i = 0; i + 1 < h.size(); i += 2) out.push_back((uint8_t)(nib(h[i]) << 4 | nib(h[i + 1])));
-        return out;
-    }
-};
-
-void put_hex(const char *name, const uint8_t *p, size_t n, const char *end = ",") {
-    static const char D[] = "0123456789abcdef";
-    std::string s(2 * n, '0');
-    for (size_t i = 0; i < n; ++i) s[2 * i] = D[p[i] >> 4], s[2 * i + 1] = D[p[i] & 15];
-    printf("\"%s\":\"%s\"%s", name, s.c_str(), end);
-}
-
-template <class T>
-void put_list(const char *name, const T *p, size_t n, const char *end = ",") {
-    printf("\"%s\":[", name);
-    for (size_t i = 0; i < n; ++i) printf("%s%llu", i ? "," : "", (unsigned long long)p[i]);
-    printf("]%s", end);
-}
 
 // the exclusive scan of counts[m] into off[m + 1]: what k_scan_* computes
 template <class T>

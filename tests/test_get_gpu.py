@@ -7,9 +7,13 @@ keys and values it put); for absent keys it is the existing lookup
 KEY_MISMATCH (approximate mode: FOUND with the slot's 8 bytes)."""
 import os
 import shutil
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from locate_cases import header_rule  # noqa: E402  (the header's rule, restated once for the host and the GPU tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -321,16 +325,6 @@ def test_approximate_mode(source, dbs):
         check(db.get_var(*pack(source["keys"] + source["absent"])), status, truth)
         db.set_batch(777)
         check(db.get_var(*pack(source["keys"] + source["absent"])), status, truth)
-
-
-def header_rule(f, size, pos, key):
-    """The status the header's rule gives a record at `pos` of a compact partition file `f` for `key`."""
-    if pos + 3 > size:
-        return BAD_ADDR
-    klen, vlen = int(f[pos]), int(f[pos + 1]) << 8 | int(f[pos + 2])
-    if pos + 3 + klen + vlen > size:
-        return BAD_ADDR
-    return FOUND if bytes(f[pos + 3: pos + 3 + klen]) == key else KEY_MISMATCH
 
 
 def test_untrusted_index(source, dbs, tmp_path):
