@@ -7,6 +7,7 @@ The package holds only what the path needs:
   writer.py       host-side mirror of the reference's BSDBWriter build stages
   reader.py       host-side mirror of the reference's SyncReader over the batched get
   builder.py      the reference's Builder for text input: lines of key<sep>value -> database (build_text, CLI)
+  diff.py         two database directories compared on the device: counts and the delta as text (diff_dirs, CLI)
 """
 from .native import BsdbError, Context, Database, IndexWriter, Mph, Multi, lib, num_buckets  # noqa: F401
 from .reader import BSDBReader  # noqa: F401

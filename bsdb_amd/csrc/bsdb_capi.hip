@@ -13,7 +13,8 @@
 // blocked layout and a database, with its plan text_plan.hpp), capi_check.hip
 // (a database checked against text input, with its plan check_plan.hpp),
 // capi_dump.hip (a resident database enumerated by slot, with its plan
-// dump_plan.hpp).
+// dump_plan.hpp), capi_diff.hip (two resident databases compared, with its
+// plan diff_plan.hpp).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -58,6 +59,7 @@
 #include "text_blocked_kernels.hip"
 #include "check_kernels.hip"
 #include "dump_kernels.hip"
+#include "diff_kernels.hip"
 
 using namespace bsdb;
 
@@ -1058,3 +1060,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_text.hip"
 #include "capi_check.hip"
 #include "capi_dump.hip"
+#include "capi_diff.hip"

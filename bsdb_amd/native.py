@@ -168,6 +168,9 @@ SIGNATURES = [
     ("bsdb_db_set_text_chunk", _i, [_vp, _u64]),
     ("bsdb_db_scan", _i, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("bsdb_db_dump_text", _i, [_vp, C.c_char_p, _i, _u64, _u64, _i, _vp]),
+    ("bsdb_dev_db_diff", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    ("bsdb_dev_db_select", _i, [_vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_db_diff", _i, [_vp, _vp, _i, C.c_char_p, C.c_char_p, _vp, _vp, _vp, _vp]),
 ]
 
 TEXT_WORDS = 10
@@ -197,6 +200,16 @@ SCAN_FIELDS = ("slots", "ok", "bad_addr", "not_text", "key_bytes", "value_bytes"
 SCAN_OK, SCAN_BAD_ADDR, SCAN_NOT_TEXT = 0, 1, 2  # a slot's status byte
 SCAN_NONE = (1 << 64) - 1  # first_bad when every slot is OK
 DUMP_MAX_LINE = 255 + 65535 + 2  # the smallest text-chunk cap: the longest line
+
+DIFF_WORDS = 10
+# the diff report's words in the header's order (uint64_t[BSDB_DIFF_WORDS])
+DIFF_FIELDS = ("slots", "same", "rejected", "key_mismatch", "bad_addr", "value_len", "value_bytes", "bad_slot", "first_diff",
+               "compared_bytes")
+DIFF_SAME, DIFF_BAD_SLOT = 0, 6  # a slot's status byte; 1 .. 3 are the get's, 4 and 5 the check's
+DIFF_NONE = (1 << 64) - 1  # first_diff when every slot is SAME
+DIFF_STATUS_NAMES = DIFF_FIELDS[1:8]  # a status byte's name is its counter's
+DIFF_MASK_ABSENT = 1 << GET_REJECTED | 1 << GET_KEY_MISMATCH  # bsdb_db_diff's removed file
+DIFF_MASK_UPSERT = DIFF_MASK_ABSENT | 1 << CHECK_VALUE_LEN | 1 << CHECK_VALUE_BYTES  # its upsert file
 
 BSDB_EVERIFY = -74
 VERIFY_WORDS = 8
@@ -381,7 +394,7 @@ class Context:
         return a.value, b.value
 
     # ---- live per-kernel timing (HIP events on the launch stream)
-    PASS1, PASS2, SCAN, CHECK_VALUES, DUMP_TEXT = 0, 1, 2, 3, 4
+    PASS1, PASS2, SCAN, CHECK_VALUES, DUMP_TEXT, DIFF_VALUES = 0, 1, 2, 3, 4, 5
 
     def set_profiling(self, on: bool):
         _check("bsdb_set_profiling", lib().bsdb_set_profiling(self._h, 1 if on else 0))
@@ -1084,6 +1097,59 @@ class Context:
             text_bytes, _ptr(status), first, _ptr(report), _stream(stream)))
         return text[:text_bytes], status, report
 
+    # ---- two resident databases compared: records(A) -> gather keys -> locate in B -> diff -> select
+    @staticmethod
+    def diff_report(device):
+        """A fresh device report for db_diff: int64[DIFF_WORDS], zero with first_diff = UINT64_MAX (-1)."""
+        import torch
+        report = torch.zeros(DIFF_WORDS, dtype=torch.int64, device=device)
+        report[8] = -1
+        return report
+
+    def db_diff(self, a: "Database", b: "Database", vsrc_a, vlen_a, status_a, src_b, vlen_b, status, slot_base: int = 0,
+                count: Optional[int] = None, report=None, stream=None):
+        """bsdb_dev_db_diff: A's values (vsrc_a int64, vlen_a int32, status_a
+        uint8 of db_records on `a`) against B's (src_b int64, vlen_b int32,
+        status uint8 of db_locate_var on `b` for the same records' keys).
+        `status` is rewritten in place to the diff's; `report`
+        (Context.diff_report, made here when not given) accumulates;
+        `slot_base` is A's slot of record 0.  Returns (status, report)."""
+        import torch
+        if count is None:
+            count = status.numel()
+        if report is None:
+            report = self.diff_report(status.device)
+        if (vsrc_a.dtype != torch.int64 or src_b.dtype != torch.int64 or vlen_a.dtype != torch.int32 or vlen_b.dtype != torch.int32
+                or status_a.dtype != torch.uint8 or status.dtype != torch.uint8 or report.dtype != torch.int64
+                or report.numel() < DIFF_WORDS
+                or min(vsrc_a.numel(), src_b.numel(), vlen_a.numel(), vlen_b.numel(), status_a.numel(), status.numel()) < count):
+            raise ValueError("vsrc_a / src_b int64[count], vlen_a / vlen_b int32[count], status_a / status uint8[count], "
+                             "report int64[DIFF_WORDS]")
+        _check("bsdb_dev_db_diff", lib().bsdb_dev_db_diff(
+            a._h, b._h, count, _ptr(vsrc_a), _ptr(vlen_a), _ptr(status_a), _ptr(src_b), _ptr(vlen_b), _ptr(status), slot_base,
+            _ptr(report), _stream(stream)))
+        return status[:count], report
+
+    def db_select(self, db: "Database", status, mask: int, ksrc, klen, vsrc, vlen, stream=None):
+        """bsdb_dev_db_select: the records whose status bit is set in `mask`,
+        in slot order: (sel int64, ksrc, klen, vsrc, vlen) cut to the number
+        selected (read back, which synchronises).  The descriptors feed
+        db_dump_text with a zeroed status array."""
+        import torch
+        count = status.numel()
+        if (status.dtype != torch.uint8 or ksrc.dtype != torch.int64 or vsrc.dtype != torch.int64 or klen.dtype != torch.int32
+                or vlen.dtype != torch.int32 or min(ksrc.numel(), vsrc.numel(), klen.numel(), vlen.numel()) < count):
+            raise ValueError("status uint8[count], ksrc / vsrc int64[count], klen / vlen int32[count]")
+        dev, k = status.device, max(count, 1)
+        sel, ksrc_o, vsrc_o = (torch.empty(k, dtype=torch.int64, device=dev) for _ in range(3))
+        klen_o, vlen_o = (torch.empty(k, dtype=torch.int32, device=dev) for _ in range(2))
+        nsel = torch.zeros(1, dtype=torch.int64, device=dev)
+        _check("bsdb_dev_db_select", lib().bsdb_dev_db_select(
+            db._h, count, _ptr(status), mask, _ptr(ksrc), _ptr(klen), _ptr(vsrc), _ptr(vlen), _ptr(sel), _ptr(ksrc_o), _ptr(klen_o),
+            _ptr(vsrc_o), _ptr(vlen_o), _ptr(nsel), _stream(stream)))
+        n = int(nsel[0])
+        return sel[:n], ksrc_o[:n], klen_o[:n], vsrc_o[:n], vlen_o[:n]
+
     # ---- text front end: lines of "key<sep>value" -> descriptors -> kv.db image
     @staticmethod
     def _sep(separator) -> int:
@@ -1396,6 +1462,11 @@ def _check_report(report) -> dict:
     return {k: int(v) & CHECK_NONE for k, v in zip(CHECK_FIELDS, report)}
 
 
+def _diff_report(report) -> dict:
+    """The diff report's words as a dict (DIFF_FIELDS, the header's order); words taken as unsigned."""
+    return {k: int(v) & DIFF_NONE for k, v in zip(DIFF_FIELDS, report)}
+
+
 class Database:
     """``bsdb_db``: a finished database resident on one device; batched gets
     key -> value (SyncReader.getAsBytes for a batch).  Borrows its Mph."""
@@ -1534,6 +1605,24 @@ class Database:
         _check("bsdb_db_dump_text", lib().bsdb_db_dump_text(
             self._h, os.fsencode(os.fspath(path)), Context._sep(separator), first, count, 1 if append else 0, report))
         return _scan_report(report)
+
+    def diff(self, other: "Database", upsert=None, removed=None, separator=" ") -> dict:
+        """bsdb_db_diff: this database (A) against `other` (B, on the same
+        Context), in both directions on the device.  `removed` receives the
+        ``key<sep>value`` lines of A's records whose key B does not hold,
+        `upsert` those of B's records that A does not hold or holds with
+        another value; either may be None.  Returns {"ab", "ba": the two
+        reports (DIFF_FIELDS), "upsert", "removed": the two files' reports
+        (SCAN_FIELDS; empty without a file), "identical": every slot of
+        either side is SAME in the other}."""
+        ab, ba = (C.c_uint64 * DIFF_WORDS)(), (C.c_uint64 * DIFF_WORDS)()
+        up, rm = (C.c_uint64 * SCAN_WORDS)(), (C.c_uint64 * SCAN_WORDS)()
+        _check("bsdb_db_diff", lib().bsdb_db_diff(
+            self._h, other._h, Context._sep(separator), None if upsert is None else os.fsencode(os.fspath(upsert)),
+            None if removed is None else os.fsencode(os.fspath(removed)), ab, ba, up, rm))
+        ab, ba = _diff_report(ab), _diff_report(ba)
+        return {"ab": ab, "ba": ba, "upsert": _scan_report(up), "removed": _scan_report(rm),
+                "identical": ab["same"] == self.info()["n"] and ba["same"] == other.info()["n"]}
 
 
 class Builder:

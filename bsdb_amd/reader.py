@@ -20,6 +20,12 @@ An exact database also lists itself, by slot (bsdb_db_scan, bsdb_db_dump_text):
 
 does the latter from the command line: exit status 0 when every slot is OK, 2
 when a slot's address names no record or a record's line does not read back.
+
+Two exact databases on one device context are compared on the device
+(bsdb_db_diff): ``BSDBReader(b_dir, ctx=a.ctx)`` borrows the context of reader
+``a`` and does not close it, and ``a.diff(b, upsert=..., removed=...)`` gives
+the counts of both directions and the delta as text (bsdb_amd/diff.py is its
+command line).
 """
 from __future__ import annotations
 
@@ -44,7 +50,7 @@ def _read_config(path: str) -> dict:
 
 
 class BSDBReader:
-    def __init__(self, base_path: str, approximate: Optional[bool] = None, device: int = 0):
+    def __init__(self, base_path: str, approximate: Optional[bool] = None, device: int = 0, ctx: Optional[Context] = None):
         cfg = _read_config(os.path.join(base_path, "config.properties"))
         if cfg.get("kv.compressed", "false").lower() == "true":
             raise NotImplementedError("compressed kv.db files are not read (the zstd layout is out of scope)")
@@ -60,7 +66,8 @@ class BSDBReader:
         if not partitions and not self.approximate:
             raise FileNotFoundError(f"{kv}.0")
         self.partitions = partitions
-        self.ctx = Context(device)
+        self._own_ctx = ctx is None  # a borrowed context is used and not closed
+        self.ctx = Context(device) if ctx is None else ctx
         self.mph = self.db = None
         try:
             self.mph = self.ctx.mph_load(os.path.join(base_path, "hash.dump"))
@@ -97,8 +104,12 @@ class BSDBReader:
         """Database.dump_text: the ``key<sep>value`` lines of the slots to `path`; returns the report."""
         return self.db.dump_text(path, separator, first, count, append)
 
+    def diff(self, other: "BSDBReader", upsert=None, removed=None, separator=" ") -> dict:
+        """Database.diff: this database against `other`'s (a reader on the same context: ``ctx=self.ctx``)."""
+        return self.db.diff(other.db, upsert, removed, separator)
+
     def close(self):
-        for o in (self.db, self.mph, self.ctx):
+        for o in (self.db, self.mph, self.ctx if self._own_ctx else None):
             if o is not None:
                 o.close()
         self.db = self.mph = None

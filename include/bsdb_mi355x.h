@@ -274,7 +274,8 @@ int bsdb_fused_status(bsdb_ctx *ctx, uint64_t *launches, uint64_t *timeouts);
  * bsdb_profile_read synchronises those events and returns, for `kind`
  * (0 = pass 1, 1 = pass 2, 2 = edge-offset scan, 3 = the value compare of
  * bsdb_dev_db_check, k_check_values alone, 4 = the text kernel of
- * bsdb_dev_db_dump_text, k_dump_text alone), the summed milliseconds, the
+ * bsdb_dev_db_dump_text, k_dump_text alone, 5 = the value compare of
+ * bsdb_dev_db_diff, k_diff_values alone; keys = records), the summed milliseconds, the
  * number of launches and the keys they processed; then clears that kind. */
 int bsdb_set_profiling(bsdb_ctx *ctx, int enable);
 int bsdb_profile_read(bsdb_ctx *ctx, int kind, double *total_ms, uint64_t *launches, uint64_t *keys);
@@ -1087,9 +1088,9 @@ int bsdb_db_check_text(bsdb_db *db, const char *const *paths, int nfiles, int se
  *   bad separator (as for bsdb_text_build), first + count > n, an approximate
  *   db or one whose MPHF was freed; count == 0 is BSDB_OK with an empty result;
  *   BSDB_EFILE for a file that cannot be written.
- * Out of scope: the diff of two databases, escaping NOT_TEXT records, other
- * line terminators, compressed kv.db, a kv.db larger than device memory, and
- * whether each slot is its own key's (bsdb_kv_verify_index: a dump presumes a
+ * The diff of two databases is the next block's (bsdb_db_diff).
+ * Out of scope: escaping NOT_TEXT records, other line terminators, compressed
+ * kv.db, a kv.db larger than device memory, and whether each slot is its own key's (bsdb_kv_verify_index: a dump presumes a
  * verified database).
  * ------------------------------------------------------------------------- */
 #define BSDB_SCAN_WORDS 8
@@ -1110,6 +1111,88 @@ int bsdb_db_scan(bsdb_db *db, uint64_t first, uint64_t count, uint64_t key_cap, 
                  uint64_t *report /* BSDB_SCAN_WORDS */);
 int bsdb_db_dump_text(bsdb_db *db, const char *path, int separator, uint64_t first, uint64_t count, int append,
                       uint64_t *report /* BSDB_SCAN_WORDS */);
+
+/* ---- two resident databases compared: same, changed, absent ----------------
+ * What changed between database A and database B, both resident on one
+ * context: every slot of A gets one status byte that says what B holds for
+ * that slot's key.  A's records are listed by slot (bsdb_dev_db_records), their
+ * keys packed (bsdb_dev_edge_offsets + bsdb_dev_db_gather) and located in B
+ * (bsdb_dev_db_locate_var); the values are then compared in place, image
+ * against image: nothing is gathered, and no record passes through host memory
+ * unless it is written to a delta file.  (The reference has no diff.)  Exact
+ * mode only.
+ *
+ * A slot's status:
+ *   0 BSDB_DIFF_SAME          B holds the key with the same value length and bytes
+ *   1 BSDB_GET_REJECTED       B's MPHF rejects the key: absent from B
+ *   2 BSDB_GET_KEY_MISMATCH   B's slot holds another key: absent from B
+ *   3 BSDB_GET_BAD_ADDR       B's slot names no whole record: B is damaged
+ *   4 BSDB_CHECK_VALUE_LEN    present in both, the value lengths differ
+ *   5 BSDB_CHECK_VALUE_BYTES  present in both, the same length, some byte differs
+ *   6 BSDB_DIFF_BAD_SLOT      A's own slot names no record (BSDB_SCAN_BAD_ADDR
+ *                             from bsdb_dev_db_records); it is not looked up
+ * The report is uint64_t[BSDB_DIFF_WORDS], ACCUMULATED by the dev_ call into
+ * words the caller zeroed, with [8] = UINT64_MAX:
+ *   [0] slots   [1] same   [2] rejected   [3] key_mismatch   [4] bad_addr
+ *   [5] value_len   [6] value_bytes   [7] bad_slot     [0] == [1] + ... + [7]
+ *   [8] first_diff: the lowest slot of A that is not SAME, UINT64_MAX when none
+ *   [9] compared_bytes: the sum of the value lengths actually compared
+ *
+ * bsdb_dev_db_diff: d_vsrc_a / d_vlen_a / d_status_a are bsdb_dev_db_records'
+ *   on A for slots [slot_base, slot_base + count), d_src_b / d_vlen_b what
+ *   bsdb_dev_db_locate_var on B returned for those records' keys; d_status
+ *   comes in as locate's and goes out as the diff's (a byte that is none of
+ *   locate's counts as BAD_ADDR).  All descriptor arrays are data: no byte
+ *   outside image A is read through A's positions and none outside image B
+ *   through B's (a position past its image reads as 0), and a length over
+ *   65 535 is VALUE_LEN, never compared.  The workspace is the context's.
+ *   Asynchronous.
+ * bsdb_dev_db_select: the records whose status bit is set in `mask` (bit s
+ *   selects status s; bit 6 or any higher bit is BSDB_EINVAL: a BAD_SLOT has
+ *   no record to write), in slot order: d_sel[j] (u64) the index in
+ *   [0, count) of the j-th selected record, d_*_out[j] its four descriptors,
+ *   *d_nsel (one u64) how many there are; every output array holds `count`
+ *   entries.  The outputs feed bsdb_dev_db_dump_lengths and
+ *   bsdb_dev_db_dump_text unchanged, with a zeroed status array.  No cursor
+ *   atomics: the output is deterministic.  Asynchronous.
+ * bsdb_db_diff: the whole comparison in both directions, A -> B over all of
+ *   A's slots, then B -> A over all of B's, each in chunks of bsdb_db_set_batch
+ *   slots of the side that is listed; never more than one chunk is held.
+ *   removed_path receives the lines key<sep>value of A's records whose A -> B
+ *   status is 1 or 2, in A's slot order; upsert_path those of B's records whose
+ *   B -> A status is 1, 2, 4 or 5 (added or changed), in B's slot order; a
+ *   chunk's text is written in pieces under the cap of bsdb_db_set_text_chunk
+ *   of the side that is listed.  `bsdb_text_build` and `bsdb_db_check_text`
+ *   read such lines.  Either path may be NULL: the two diff reports are still
+ *   complete.  scan_upsert / scan_removed are the dump's reports
+ *   (BSDB_SCAN_WORDS) of the two files: [0] the lines written, [3] not_text
+ *   whether the text carries every record, [7] the first such line of the
+ *   file; empty for a NULL path.  Returns BSDB_OK whatever the statuses.
+ *   Two verified databases give report_ab[1] == report_ba[1], [5] == [5] and
+ *   [6] == [6].
+ * All: BSDB_EINVAL before any device call for null or misaligned arguments, an
+ *   approximate database on either side, two databases that are not on the
+ *   same context, one whose MPHF was freed, or a bad separator; BSDB_EFILE for
+ *   a file that cannot be written; count == 0 and n == 0 are BSDB_OK with zero
+ *   counts.
+ * Out of scope: approximate databases, databases on different devices, two
+ * databases that do not fit the device together (bsdb_db_open answers
+ * BSDB_ENOMEM), compressed kv.db, and applying a delta (bsdb_db_dump_text, an
+ * edit of the text and bsdb_text_build do that).
+ * ------------------------------------------------------------------------- */
+#define BSDB_DIFF_WORDS 10
+#define BSDB_DIFF_SAME 0
+#define BSDB_DIFF_BAD_SLOT 6
+int bsdb_dev_db_diff(bsdb_db *a, bsdb_db *b, uint64_t count, const uint64_t *d_vsrc_a, const uint32_t *d_vlen_a,
+                     const uint8_t *d_status_a, const uint64_t *d_src_b, const uint32_t *d_vlen_b, uint8_t *d_status,
+                     uint64_t slot_base, uint64_t *d_report /* BSDB_DIFF_WORDS */, void *stream);
+int bsdb_dev_db_select(bsdb_db *db, uint64_t count, const uint8_t *d_status, uint32_t mask, const uint64_t *d_ksrc,
+                       const uint32_t *d_klen, const uint64_t *d_vsrc, const uint32_t *d_vlen, uint64_t *d_sel,
+                       uint64_t *d_ksrc_out, uint32_t *d_klen_out, uint64_t *d_vsrc_out, uint32_t *d_vlen_out,
+                       uint64_t *d_nsel, void *stream);
+int bsdb_db_diff(bsdb_db *a, bsdb_db *b, int separator, const char *upsert_path, const char *removed_path,
+                 uint64_t *report_ab /* BSDB_DIFF_WORDS */, uint64_t *report_ba /* BSDB_DIFF_WORDS */,
+                 uint64_t *scan_upsert /* BSDB_SCAN_WORDS */, uint64_t *scan_removed /* BSDB_SCAN_WORDS */);
 
 #ifdef __cplusplus
 }
