@@ -60,6 +60,7 @@
 #include "check_kernels.hip"
 #include "dump_kernels.hip"
 #include "diff_kernels.hip"
+#include "merge_kernels.hip"
 
 using namespace bsdb;
 
@@ -1061,3 +1062,4 @@ int bsdb_hash_var(bsdb_ctx *c, const uint8_t *h_blob, const uint64_t *h_off, uin
 #include "capi_check.hip"
 #include "capi_dump.hip"
 #include "capi_diff.hip"
+#include "capi_merge.hip"

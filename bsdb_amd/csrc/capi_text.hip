@@ -80,6 +80,7 @@ struct TextPackIO {
     uint8_t *d_blob;
     uint64_t blob_cap, *d_off, *h_blob_bytes, *d_value8;
     uint8_t *d_value_len;
+    bool from_image = false;  // the records lie in a resident image (capi_merge.hip): d.kpos / d.vpos and d_text are unused
 };
 
 bool text_pack_bad_args(const bsdb_ctx *c, const TextPackIO &io) {
@@ -91,14 +92,17 @@ bool text_pack_bad_args(const bsdb_ctx *c, const TextPackIO &io) {
            (!io.d_value8 != !io.d_value_len) || (((uintptr_t)io.d_addr | (uintptr_t)io.d_off | (uintptr_t)io.d_value8) & 7);
 }
 
-// A pack under way: what text_pack_impl hands to the layout's placement and
-// what the placement finds out.
+// A pack under way: what a pack hands to the layout's placement and what the
+// placement finds out.  The placement works on sizes alone: whose records they
+// are (a chunk of text, a resident image: capi_merge.hip) is the pack's.
 struct TextPlacing {
     TextRuns runs{};
-    TextPack pack{};                 // the chunk and its records; dst / off per launch
     uint32_t *rsize, *ksize;         // [count] the records' bytes in the image and in the key blob
     uint32_t lgrid;                  // a record per lane
+    unsigned long long *sizes_report = nullptr;  // k_rec_sizes' (the merge's report), else null: k_text_sizes
     const uint64_t *roff = nullptr;  // compact: the scan of rsize, the addresses' offsets
+    const uint64_t *PS = nullptr, *PL = nullptr;  // blocked: k_blk_place's position lists
+    uint64_t image_bytes = 0;
     uint64_t blob_bytes = 0;
     uint64_t run[TEXT_MAX_PARTS] = {};
 };
@@ -107,7 +111,8 @@ struct TextPlacing {
 // scan sized -> scan and the key blob's offsets.
 int text_sizes(bsdb_ctx *c, const TextPackIO &io, const TextPlacing &pl, uint32_t *ssize, const uint32_t *sized, uint64_t *scan,
                hipStream_t s) {
-    k_text_sizes<<<pl.lgrid, 256, 0, s>>>(io.d.klen, io.d.vlen, io.count, io.B, pl.rsize, pl.ksize, ssize);
+    if (io.from_image) k_rec_sizes<<<pl.lgrid, 256, 0, s>>>(io.d.klen, io.d.vlen, io.count, io.B, pl.rsize, pl.ksize, ssize, pl.sizes_report);
+    else k_text_sizes<<<pl.lgrid, 256, 0, s>>>(io.d.klen, io.d.vlen, io.count, io.B, pl.rsize, pl.ksize, ssize);
     int rc;
     if ((rc = text_scan(c, sized, io.count, scan, s))) return rc;
     return io.d_off ? text_scan(c, pl.ksize, io.count, io.d_off, s) : BSDB_OK;
@@ -150,7 +155,7 @@ int text_place_compact(bsdb_ctx *c, const TextPackIO &io, TextPlacing &pl, hipSt
         if (io.h_part_size[p] > TEXT_MAX_FILE || pl.run[p] > TEXT_MAX_FILE - io.h_part_size[p]) return BSDB_EINVAL;
         pl.runs.file_base[p] = io.h_part_size[p] - at[p];  // (+ roff[r] >= at[p]: the sum never wraps past the file offset)
     }
-    if (io.d_image) text_pack_launch<true>(c, pl.pack, roff, io.d_image, image_bytes, s);
+    pl.image_bytes = image_bytes;
     return BSDB_OK;
 }
 
@@ -194,46 +199,65 @@ int text_place_blocked(bsdb_ctx *c, const TextPackIO &io, TextPlacing &pl, hipSt
     if (io.d_image || io.d_addr)
         k_blk_place<<<text_lane_grid(count + 1, c->num_cus), 256, 0, s>>>(runs, br, E, pl.rsize, boff, bend, count, B, image_bytes, PS,
                                                                            PL, io.d_addr);
-    if (io.d_image && image_bytes) {
-        TextPackBlocked b{pl.pack, PS, PL, B};
-        b.t.dst = io.d_image;
-        b.t.out_bytes = image_bytes;
-        k_text_pack_blocked<<<piece_grid(image_bytes, (uint32_t)((uintptr_t)io.d_image & 15), c->num_cus), 256, 0, s>>>(b);
-    }
+    pl.PS = PS, pl.PL = PL;
+    pl.image_bytes = image_bytes;
     return BSDB_OK;
 }
 
-// The pack of one chunk's `count` records; the caller holds the context's lock
-// and has set the device.  The layout's placement waits once, for the sizes
-// (they go back to the host, and nothing is written before they are known to
-// fit) and launches the image's kernel; the key blob and the value heads
-// follow it.
-int text_pack_impl(bsdb_ctx *c, const TextPackIO &io, hipStream_t s) {
-    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = 0;
-    if (io.h_blob_bytes) *io.h_blob_bytes = 0;
-    if (!io.count) {
-        if (io.d_off) HIP_OK(hipMemsetAsync(io.d_off, 0, 8, s));
-        return BSDB_OK;
-    }
+// The placement of one chunk's `count` >= 1 records, for either pack: the runs
+// of the partition rule, the sizes and the layout's placement, which waits
+// once, for the sizes (they go back to the host, and nothing is written before
+// they are known to fit).
+int text_place(bsdb_ctx *c, const TextPackIO &io, TextPlacing &pl, hipStream_t s) {
     int rc;
     if ((rc = c->t_size.grow(2 * 4 * io.count))) return rc;
-    TextPlacing pl;
     pl.rsize = c->t_size.as<uint32_t>();
     pl.ksize = pl.rsize + io.count;
     pl.lgrid = text_lane_grid(io.count, c->num_cus);
     pl.runs.partitions = (uint32_t)io.partitions;
     for (int p = 0; p <= io.partitions; ++p) pl.runs.bound[p] = text_run_bound(io.count, (uint32_t)io.partitions, (uint32_t)p);
-    pl.pack = {io.d_text, io.bytes, io.d.kpos, io.d.klen, io.d.vpos, io.d.vlen, io.count, nullptr, nullptr, 0};
-    if ((rc = io.B ? text_place_blocked(c, io, pl, s) : text_place_compact(c, io, pl, s))) return rc;
-    if (io.d_blob && pl.blob_bytes) text_pack_launch<false>(c, pl.pack, io.d_off, io.d_blob, pl.blob_bytes, s);
+    return io.B ? text_place_blocked(c, io, pl, s) : text_place_compact(c, io, pl, s);
+}
+
+// what every pack reports when it has launched everything
+int text_pack_done(const TextPackIO &io, const TextPlacing &pl) {
+    const int rc = launch_status();
+    if (rc) return rc;
+    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = pl.run[p];
+    if (io.h_blob_bytes) *io.h_blob_bytes = pl.blob_bytes;
+    return BSDB_OK;
+}
+
+// a pack of no record
+int text_pack_empty(const TextPackIO &io, hipStream_t s) {
+    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = 0;
+    if (io.h_blob_bytes) *io.h_blob_bytes = 0;
+    if (!io.count && io.d_off) HIP_OK(hipMemsetAsync(io.d_off, 0, 8, s));
+    return BSDB_OK;
+}
+
+// The pack of one chunk's `count` records; the caller holds the context's lock
+// and has set the device.  After the placement the image's kernel is
+// launched; the key blob and the value heads follow it.
+int text_pack_impl(bsdb_ctx *c, const TextPackIO &io, hipStream_t s) {
+    int rc;
+    if ((rc = text_pack_empty(io, s)) || !io.count) return rc;
+    TextPlacing pl;
+    if ((rc = text_place(c, io, pl, s))) return rc;
+    const TextPack pack{io.d_text, io.bytes, io.d.kpos, io.d.klen, io.d.vpos, io.d.vlen, io.count, nullptr, nullptr, 0};
+    if (io.d_image && !io.B) text_pack_launch<true>(c, pack, pl.roff, io.d_image, pl.image_bytes, s);
+    if (io.d_image && io.B && pl.image_bytes) {
+        TextPackBlocked b{pack, pl.PS, pl.PL, io.B};
+        b.t.dst = io.d_image;
+        b.t.out_bytes = pl.image_bytes;
+        k_text_pack_blocked<<<piece_grid(pl.image_bytes, (uint32_t)((uintptr_t)io.d_image & 15), c->num_cus), 256, 0, s>>>(b);
+    }
+    if (io.d_blob && pl.blob_bytes) text_pack_launch<false>(c, pack, io.d_off, io.d_blob, pl.blob_bytes, s);
     uint64_t *const d_addr = pl.roff ? io.d_addr : nullptr;  // (the blocked addresses are k_blk_place's)
     if (d_addr || io.d_value8)
         k_text_outputs<<<pl.lgrid, 256, 0, s>>>(pl.runs, io.d_text, io.bytes, io.d.vpos, io.d.vlen, pl.roff, io.count, d_addr,
                                                  io.d_value8, io.d_value_len);
-    if ((rc = launch_status())) return rc;
-    for (int p = 0; p < io.partitions; ++p) io.h_run_bytes[p] = pl.run[p];
-    if (io.h_blob_bytes) *io.h_blob_bytes = pl.blob_bytes;
-    return BSDB_OK;
+    return text_pack_done(io, pl);
 }
 
 // bsdb_dev_text_pack(_blocked) after their argument checks

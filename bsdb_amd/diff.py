@@ -10,8 +10,8 @@ that A does not hold or holds with another value (in B's slot order),
 
 prints one line of counts per direction; exit status 0 when the two hold the
 same records, 2 when they do not.  Exact databases only; both must fit the
-device together.  Applying a delta is dump_text, an edit of the text and
-build_text.
+device together.  Applying a delta: build the two files into small databases
+(``build_text``) and merge them over A (``python -m bsdb_amd.merge``).
 """
 from __future__ import annotations
 

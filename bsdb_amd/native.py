@@ -171,6 +171,10 @@ SIGNATURES = [
     ("bsdb_dev_db_diff", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     ("bsdb_dev_db_select", _i, [_vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("bsdb_db_diff", _i, [_vp, _vp, _i, C.c_char_p, C.c_char_p, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_merge_status", _i, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsdb_dev_db_pack", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _i, _i, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp,
+                              C.POINTER(_u64), _vp, _vp, _vp]),
+    ("bsdb_db_merge", _i, [_vp, _vp, _vp, C.c_char_p, _i, _i, _u32, _u32, _i, C.c_char_p, C.c_char_p, _vp, C.POINTER(_vp)]),
 ]
 
 TEXT_WORDS = 10
@@ -210,6 +214,13 @@ DIFF_NONE = (1 << 64) - 1  # first_diff when every slot is SAME
 DIFF_STATUS_NAMES = DIFF_FIELDS[1:8]  # a status byte's name is its counter's
 DIFF_MASK_ABSENT = 1 << GET_REJECTED | 1 << GET_KEY_MISMATCH  # bsdb_db_diff's removed file
 DIFF_MASK_UPSERT = DIFF_MASK_ABSENT | 1 << CHECK_VALUE_LEN | 1 << CHECK_VALUE_BYTES  # its upsert file
+
+MERGE_WORDS = 12
+# the merge report's words in the header's order (uint64_t[BSDB_MERGE_WORDS])
+MERGE_FIELDS = ("base_slots", "kept", "replaced", "removed", "bad_slot", "bad_addr", "delta_slots", "delta_written",
+                "delta_bad_slot", "out_records", "out_key_bytes", "out_value_bytes")
+MERGE_KEPT, MERGE_REPLACED, MERGE_REMOVED, MERGE_BAD_SLOT, MERGE_BAD_ADDR = range(5)  # a slot of base after the merge
+MERGE_MAX_RECORD = 3 + TEXT_MAX_KEY + TEXT_MAX_VALUE  # the longest record a pack writes
 
 BSDB_EVERIFY = -74
 VERIFY_WORDS = 8
@@ -394,7 +405,7 @@ class Context:
         return a.value, b.value
 
     # ---- live per-kernel timing (HIP events on the launch stream)
-    PASS1, PASS2, SCAN, CHECK_VALUES, DUMP_TEXT, DIFF_VALUES = 0, 1, 2, 3, 4, 5
+    PASS1, PASS2, SCAN, CHECK_VALUES, DUMP_TEXT, DIFF_VALUES, REC_PACK = 0, 1, 2, 3, 4, 5, 6
 
     def set_profiling(self, on: bool):
         _check("bsdb_set_profiling", lib().bsdb_set_profiling(self._h, 1 if on else 0))
@@ -1150,6 +1161,73 @@ class Context:
         n = int(nsel[0])
         return sel[:n], ksrc_o[:n], klen_o[:n], vsrc_o[:n], vlen_o[:n]
 
+    # ---- resident databases merged: records(base) -> locate in delta / removed -> status -> select -> pack
+    def db_merge_status(self, status_base, status_delta=None, status_removed=None, report=None, stream=None):
+        """bsdb_dev_db_merge_status: db_records' status of base's slots and
+        locate's statuses of their keys in delta / removed (either None: that
+        database is not there), all uint8[count], into the merge's status
+        byte.  `report` int64[MERGE_WORDS] (zeros when made here)
+        accumulates.  Returns (status, report); ``db_select(db, status, 1 <<
+        MERGE_KEPT, ...)`` gives the records that go on."""
+        import torch
+        count = status_base.numel()
+        for t in (status_base, status_delta, status_removed):
+            if t is not None and (t.dtype != torch.uint8 or t.numel() < count):
+                raise ValueError("status arrays are uint8[count]")
+        if report is None:
+            report = torch.zeros(MERGE_WORDS, dtype=torch.int64, device=status_base.device)
+        elif report.dtype != torch.int64 or report.numel() < MERGE_WORDS:
+            raise ValueError("report int64[MERGE_WORDS]")
+        out = torch.empty(max(count, 1), dtype=torch.uint8, device=status_base.device)
+        _check("bsdb_dev_db_merge_status", lib().bsdb_dev_db_merge_status(
+            self._h, count, _ptr(status_base), None if status_delta is None else _ptr(status_delta),
+            None if status_removed is None else _ptr(status_removed), _ptr(out), _ptr(report), _stream(stream)))
+        return out[:count], report
+
+    def db_pack(self, db: "Database", ksrc, klen, vsrc, vlen, partitions: int, part_sizes, approximate: bool = False,
+                count: Optional[int] = None, image=None, addr=None, blob=None, off=None, value8=None, value_len=None,
+                stream=None, block_size: Optional[int] = None, want_image: bool = True) -> dict:
+        """bsdb_dev_db_pack: the records of db's resident image that the
+        descriptors name (db_records' or db_select's: ksrc / vsrc int64, klen /
+        vlen int32) into a kv.db image, compact or -- with `block_size` --
+        blocked.  Arguments and result as text_pack's."""
+        import numpy as np
+        import torch
+        if count is None:
+            count = ksrc.numel()
+        if (ksrc.dtype != torch.int64 or vsrc.dtype != torch.int64 or klen.dtype != torch.int32 or vlen.dtype != torch.int32
+                or min(ksrc.numel(), vsrc.numel(), klen.numel(), vlen.numel()) < count):
+            raise ValueError("ksrc / vsrc int64[count], klen / vlen int32[count]")
+        dev = ksrc.device
+        sizes = np.ascontiguousarray(part_sizes, np.uint64)
+        if sizes.size != partitions:
+            raise ValueError("one size per partition")
+        most = count * MERGE_MAX_RECORD
+        if image is None and want_image:
+            image = torch.empty((2 * most + partitions * block_size if block_size else most) + 16, dtype=torch.uint8, device=dev)
+        if blob is None:
+            blob = torch.empty(count * TEXT_MAX_KEY + 16, dtype=torch.uint8, device=dev)
+        if addr is None:
+            addr = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        if off is None:
+            off = torch.empty(count + 1, dtype=torch.int64, device=dev)
+        if approximate and value8 is None:
+            value8 = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        if approximate and value_len is None:
+            value_len = torch.empty(max(count, 1), dtype=torch.uint8, device=dev)
+        if addr.numel() < count or off.numel() < count + 1 or (approximate and min(value8.numel(), value_len.numel()) < count):
+            raise ValueError("addr / value8 / value_len hold count entries, off count + 1")
+        runs = np.zeros(partitions, np.uint64)
+        blob_bytes = C.c_uint64()
+        _check("bsdb_dev_db_pack", lib().bsdb_dev_db_pack(
+            self._h, db._h, _ptr(ksrc), _ptr(klen), _ptr(vsrc), _ptr(vlen), count, partitions, 0 if block_size is None else 1,
+            block_size or 0, sizes.ctypes.data, _ptr(image) if want_image else None, image.numel() if want_image else 0,
+            runs.ctypes.data, _ptr(addr), _ptr(blob), blob.numel(), _ptr(off), C.byref(blob_bytes),
+            _ptr(value8) if approximate else None, _ptr(value_len) if approximate else None, _stream(stream)))
+        return {"image": image[: int(runs.sum())] if want_image else None, "run_bytes": [int(x) for x in runs], "addr": addr[:count],
+                "blob": blob[: blob_bytes.value], "off": off[: count + 1],
+                "value8": value8[:count] if approximate else None, "value_len": value_len[:count] if approximate else None}
+
     # ---- text front end: lines of "key<sep>value" -> descriptors -> kv.db image
     @staticmethod
     def _sep(separator) -> int:
@@ -1623,6 +1701,28 @@ class Database:
         ab, ba = _diff_report(ab), _diff_report(ba)
         return {"ab": ab, "ba": ba, "upsert": _scan_report(up), "removed": _scan_report(rm),
                 "identical": ab["same"] == self.info()["n"] and ba["same"] == other.info()["n"]}
+
+
+    def merge(self, kv_base: str, partitions: int, width: int, index_path: str, index_a_path: Optional[str] = None,
+              approximate: bool = False, fmt: int = 0, block_size: int = 4096, delta: Optional["Database"] = None,
+              removed: Optional["Database"] = None):
+        """bsdb_db_merge: this database (base), `delta`'s records over it and
+        `removed`'s keys out of it (both on the same Context, either may be
+        None: a rebuild) into new kv.db files at `kv_base` and new index
+        files.  Returns (report dict (MERGE_FIELDS), Mph).  A damaged input
+        stops the merge: BsdbError with code BSDB_EVERIFY and the report up to
+        that chunk in ``.merge_report``; every other failure carries it too."""
+        report = (C.c_uint64 * MERGE_WORDS)()
+        h = C.c_void_p()
+        rc = lib().bsdb_db_merge(self._h, delta._h if delta is not None else None, removed._h if removed is not None else None,
+                                 os.fsencode(kv_base), partitions, fmt, block_size, width, 1 if approximate else 0,
+                                 os.fsencode(index_path), os.fsencode(index_a_path) if index_a_path else None, report, C.byref(h))
+        rep = {k: int(v) for k, v in zip(MERGE_FIELDS, report)}
+        if rc != BSDB_OK:
+            e = BsdbError("bsdb_db_merge", rc)
+            e.merge_report = rep
+            raise e
+        return rep, Mph(h, self.mph.ctx)
 
 
 class Builder:

@@ -61,7 +61,8 @@ extern "C" {
 #define BSDB_ESEEDS    (-34)  /* a bucket exhausted its 255 local seeds (GOV:431)          */
 #define BSDB_ECOMM     (-70)  /* RCCL unavailable or a collective failed                   */
 #define BSDB_EFILE     (-9)   /* file open/read/write failed (index / dump files)          */
-#define BSDB_EVERIFY   (-74)  /* a built MPHF failed its on-device bijection check         */
+#define BSDB_EVERIFY   (-74)  /* a built MPHF failed its on-device bijection check; a merge */
+                              /* stopped on a damaged input (bsdb_db_merge)                 */
 
 typedef struct bsdb_ctx bsdb_ctx;
 
@@ -275,7 +276,8 @@ int bsdb_fused_status(bsdb_ctx *ctx, uint64_t *launches, uint64_t *timeouts);
  * (0 = pass 1, 1 = pass 2, 2 = edge-offset scan, 3 = the value compare of
  * bsdb_dev_db_check, k_check_values alone, 4 = the text kernel of
  * bsdb_dev_db_dump_text, k_dump_text alone, 5 = the value compare of
- * bsdb_dev_db_diff, k_diff_values alone; keys = records), the summed milliseconds, the
+ * bsdb_dev_db_diff, k_diff_values alone, 6 = the image pack of
+ * bsdb_dev_db_pack, k_rec_pack<true> or k_rec_pack_blocked alone; keys = records), the summed milliseconds, the
  * number of launches and the keys they processed; then clears that kind. */
 int bsdb_set_profiling(bsdb_ctx *ctx, int enable);
 int bsdb_profile_read(bsdb_ctx *ctx, int kind, double *total_ms, uint64_t *launches, uint64_t *keys);
@@ -1177,8 +1179,8 @@ int bsdb_db_dump_text(bsdb_db *db, const char *path, int separator, uint64_t fir
  *   counts.
  * Out of scope: approximate databases, databases on different devices, two
  * databases that do not fit the device together (bsdb_db_open answers
- * BSDB_ENOMEM), compressed kv.db, and applying a delta (bsdb_db_dump_text, an
- * edit of the text and bsdb_text_build do that).
+ * BSDB_ENOMEM), and compressed kv.db.  Applying a delta is the next block's
+ * (bsdb_db_merge).
  * ------------------------------------------------------------------------- */
 #define BSDB_DIFF_WORDS 10
 #define BSDB_DIFF_SAME 0
@@ -1193,6 +1195,99 @@ int bsdb_dev_db_select(bsdb_db *db, uint64_t count, const uint8_t *d_status, uin
 int bsdb_db_diff(bsdb_db *a, bsdb_db *b, int separator, const char *upsert_path, const char *removed_path,
                  uint64_t *report_ab /* BSDB_DIFF_WORDS */, uint64_t *report_ba /* BSDB_DIFF_WORDS */,
                  uint64_t *scan_upsert /* BSDB_SCAN_WORDS */, uint64_t *scan_removed /* BSDB_SCAN_WORDS */);
+
+/* ---- resident databases merged into a new directory: delta over base -------
+ * merge(base, delta, removed) -> new kv.db files + index files.  All three are
+ * exact databases resident on one context; delta and removed may be NULL.  The
+ * output holds every record of delta, and every record of base whose key
+ * neither delta nor removed holds.  Of removed only the keys matter; a key in
+ * both delta and removed is in the output with delta's value.  With delta and
+ * removed NULL the call is a rebuild: the same records into another partition
+ * count, layout, signature width or approximate mode.  No record passes
+ * through text: a record whose key or value holds the separator, LF or CR
+ * (BSDB_SCAN_NOT_TEXT) is carried like any other.  (The reference has no
+ * merge.)
+ *
+ * Record order: base's kept records in base's slot order, then delta's in
+ * delta's slot order.  The records one pack writes are cut into `partitions`
+ * runs by bsdb_text_build's rule (run p = records [p k / P, (p + 1) k / P)) and
+ * appended to kv.db.<p>, in the layout bsdb_text_build_layout writes.
+ *
+ * A slot of base gets one status byte:
+ *   0 BSDB_MERGE_KEPT       it goes on
+ *   1 BSDB_MERGE_REPLACED   delta holds the key (locate: BSDB_GET_FOUND)
+ *   2 BSDB_MERGE_REMOVED    removed holds it and delta does not
+ *   3 BSDB_MERGE_BAD_SLOT   base's own slot names no record (BSDB_SCAN_BAD_ADDR);
+ *                           it has no key and is not looked up
+ *   4 BSDB_MERGE_BAD_ADDR   locate in delta or in removed returned
+ *                           BSDB_GET_BAD_ADDR, or a status byte that is no code;
+ *                           it wins over what the other database answers
+ * BSDB_GET_REJECTED and BSDB_GET_KEY_MISMATCH both mean absent.
+ * The report is uint64_t[BSDB_MERGE_WORDS], ACCUMULATED by the dev_ calls into
+ * words the caller zeroed:
+ *   [0] base_slots  [1] kept  [2] replaced  [3] removed  [4] bad_slot
+ *   [5] bad_addr    [6] delta_slots  [7] delta_written  [8] delta_bad_slot
+ *   [9] out_records [10] out_key_bytes  [11] out_value_bytes
+ *   [0] == [1] + ... + [5] and, for bsdb_db_merge, [9] == [1] + [7], for any
+ *   input.
+ *
+ * bsdb_dev_db_merge_status: d_status_base is bsdb_dev_db_records' status of
+ *   base's slots, d_status_delta / d_status_removed what
+ *   bsdb_dev_db_locate_var returned for those records' keys in delta / removed
+ *   (either may be NULL: that database is not there); d_status_out gets the
+ *   merge's status, words [0] .. [5] of d_report the counts.  Its output feeds
+ *   bsdb_dev_db_select with mask 1 << BSDB_MERGE_KEPT.  Asynchronous.
+ * bsdb_dev_db_pack: `count` records of db's resident image, named by the
+ *   descriptors bsdb_dev_db_records or bsdb_dev_db_select gave, into the image
+ *   of a kv.db chunk: the argument list and the outputs of bsdb_dev_text_pack
+ *   (format 0) / bsdb_dev_text_pack_blocked (format 1, block_size), byte for
+ *   byte what those write for the same records, with the same refusals
+ *   (BSDB_EINVAL for misaligned descriptor or output arrays, a bad block size,
+ *   h_part_size no multiple of 4096 for the blocked layout, and -- after the
+ *   sizes are known, before anything is written -- an image or key blob over
+ *   its cap; bsdb_text_image_max does not apply: 16 + the records' bytes hold a
+ *   compact image, 16 + twice that + partitions x block_size a blocked one).
+ *   Positions are u64 at any alignment.  Every position and length is data: a
+ *   length is cut to 255 (key) / 32 510 (value) wherever it is used, a position
+ *   at or past the image's end reads as zeros, and nothing is written outside
+ *   the caller's buffers.  Waits once, for the sizes.
+ * bsdb_db_merge: the whole merge.  base in chunks of bsdb_db_set_batch slots:
+ *   records, keys gathered, located in delta and in removed, status, select,
+ *   then the selection in packs whose image stays under base's
+ *   bsdb_db_set_text_chunk cap (a single record above it goes alone), each
+ *   image to the host, its runs appended to kv.db.<p>, its records added to a
+ *   streaming builder on the device; then delta in chunks of its own setting,
+ *   every record written; then bsdb_builder_finish writes index_path (and
+ *   index_a_path when `approximate`, which must then be given) with
+ *   `width` = hash.checksum.bits.  A merge must not lose records silently: if
+ *   bad_slot, bad_addr or delta_bad_slot is non-zero after a chunk, the call
+ *   stops there with BSDB_EVERIFY, the report filled up to that chunk and no
+ *   index file written (the kv.db files are incomplete).  Values over 32 510
+ *   bytes, which no writer of this project produces, are cut to that length.
+ * All: BSDB_EINVAL before any device call for null or misaligned arguments, an
+ *   approximate input, inputs on different contexts, one whose MPHF was freed,
+ *   bad partitions, format or block size, `approximate` without index_a_path;
+ *   BSDB_EFILE for a file that cannot be written.
+ * Out of scope: compressed kv.db, approximate inputs, inputs that do not fit
+ * one device together, more than one delta per call.
+ * ------------------------------------------------------------------------- */
+#define BSDB_MERGE_WORDS 12
+#define BSDB_MERGE_KEPT 0
+#define BSDB_MERGE_REPLACED 1
+#define BSDB_MERGE_REMOVED 2
+#define BSDB_MERGE_BAD_SLOT 3
+#define BSDB_MERGE_BAD_ADDR 4
+int bsdb_dev_db_merge_status(bsdb_ctx *ctx, uint64_t count, const uint8_t *d_status_base, const uint8_t *d_status_delta,
+                             const uint8_t *d_status_removed, uint8_t *d_status_out,
+                             uint64_t *d_report /* BSDB_MERGE_WORDS */, void *stream);
+int bsdb_dev_db_pack(bsdb_ctx *ctx, bsdb_db *db, const uint64_t *d_ksrc, const uint32_t *d_klen, const uint64_t *d_vsrc,
+                     const uint32_t *d_vlen, uint64_t count, int partitions, int format, uint32_t block_size,
+                     const uint64_t *h_part_size, uint8_t *d_image, uint64_t image_cap, uint64_t *h_run_bytes,
+                     uint64_t *d_addr, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_off, uint64_t *h_blob_bytes,
+                     uint64_t *d_value8, uint8_t *d_value_len, void *stream);
+int bsdb_db_merge(bsdb_db *base, bsdb_db *delta, bsdb_db *removed, const char *kv_base, int partitions, int format,
+                  uint32_t block_size, uint32_t width, int approximate, const char *index_path, const char *index_a_path,
+                  uint64_t *report /* BSDB_MERGE_WORDS */, bsdb_mph **out);
 
 #ifdef __cplusplus
 }
